@@ -10,10 +10,17 @@ split over the N GPUs).  Rank 0 prints one JSON line.
 `--gpus N` (N > 1) without a torch.distributed.run environment starts the N
 ranks itself: a child `python -m torch.distributed.run --nproc-per-node N`
 launched before this process touches the GPU, one rank per GPU over RCCL.
-With N > 1 the compressed shards are then gathered to rank 0 (gatherv) and
-scattered back for decode, timed separately from `value` (C4).
+With N > 1 and `--full` the compressed shards are then gathered to rank 0
+(gatherv) and scattered back for decode, timed separately from `value` (C4).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--strong] [--no-cpu]
+A plain run does only what `value` needs: set-up, the warm-up steps, the K
+timed steps, their round-trip check and the line.  `--full` adds every other
+line of the record (C3 decode-only, the sidecar-less and 1-state lines, the C5
+sweep, the CPU baseline, the host-call latencies and, with N > 1, the C4
+exchange), each of which a `--no-...` option still leaves out.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/*.npy.
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR] [--strong]
 """
 from __future__ import annotations
 
@@ -41,6 +48,13 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the side lines of the record (C3, sidecar-less, "
+                         "1-state, C5 sweep, CPU baseline, host calls; N > 1: the C4 exchange); a plain run "
+                         "measures and verifies the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (compressed blocks, lengths, sidecar, decoded "
+                         "bytes, statuses; fixed seeded samples of the large ones) as DIR/<name>.npy")
     ap.add_argument("--bytes", type=int, default=1 << 30,
                     help="raw bytes per GPU (weak scaling) or in total (--strong)")
     ap.add_argument("--strong", action="store_true",
@@ -79,7 +93,13 @@ def parse():
                          "prints the line, the exchange marked as timed out) instead of hanging in a collective")
     ap.add_argument("--scheme", default="round_robin", choices=("round_robin", "contiguous"),
                     help="block -> rank mapping of the gather/scatter (C4: block b on GPU b mod N)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:  # a plain run: the timed steps only
+        args.no_cpu = args.no_c3 = args.no_serial = args.no_onestate = True
+        args.no_sweep = args.no_host_calls = args.no_gather = True
+    return args
 
 
 def self_launch(args) -> None:
@@ -486,6 +506,64 @@ def roofline(kernel: str, ms: float, alg_bytes: int, what: str, profiled: bool =
             "algorithmic_bytes_per_launch": alg_bytes, "timed": what}
 
 
+DUMP_SEED = 0x5EEDD0  # the samples of --dump-outputs: the same elements in every run
+DUMP_DECODED = 1 << 21  # sampled bytes of the decoded output
+DUMP_BLOCKS = 64  # sampled compressed blocks, written whole
+DUMP_SIDECAR = 1 << 19  # sampled sidecar words
+
+
+def dump_outputs(path: str, codec, cb: dict, out, dstat) -> None:
+    """--dump-outputs: what a caller of the timed step holds after its last
+    run, as float32 / float64 .npy files under `path` (every value an exact
+    integer).  Small outputs are written whole; of the large ones (decoded
+    bytes, compressed slots, sidecar) a fixed sample drawn with DUMP_SEED,
+    and of every compressed block two checksums over its comp_len bytes.  A
+    slot's bytes past comp_len are not output (never written) and are left
+    out.  ~41 MB at the default size."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    dev = out.device
+    rng = np.random.default_rng(DUMP_SEED)
+    n = int(out.numel())
+    nb = codec.n_blocks(n)
+
+    def save(name, t, dtype=np.float32):
+        np.save(os.path.join(path, name + ".npy"), t.cpu().numpy().astype(dtype))
+
+    def pick(total, k):  # k sorted indices below total (all of them if total <= k)
+        if total <= k:
+            return torch.arange(total, device=dev)
+        return torch.from_numpy(np.sort(rng.choice(total, size=k, replace=False))).to(dev)
+
+    for name, t in (("comp_len", cb["comp_len"]), ("payload_bits", cb["payload_bits"]),
+                    ("encode_status", cb["status"]), ("decode_status", dstat)):
+        save(name, t[:nb], np.float64)
+    idx = pick(n, DUMP_DECODED)
+    save("decoded", out[idx])
+    # compressed bytes: per-block sums (plain and position-weighted) over all
+    # blocks, and the sampled blocks in full, zero past comp_len
+    slots = cb["out"].view(nb, codec.slot_bytes)
+    lens = cb["comp_len"][:nb].to(torch.int64)
+    col = torch.arange(codec.slot_bytes, device=dev)
+    weight = col % 251 + 1
+    sums = torch.empty(nb, 2, dtype=torch.int64, device=dev)
+    for b0 in range(0, nb, 512):
+        s = slots[b0:b0 + 512].to(torch.int64) * (col[None, :] < lens[b0:b0 + 512, None])
+        sums[b0:b0 + 512, 0] = s.sum(1)
+        sums[b0:b0 + 512, 1] = (s * weight[None, :]).sum(1)
+    save("compressed_block_sums", sums, np.float64)
+    bidx = pick(nb, DUMP_BLOCKS)
+    save("compressed_block_index", bidx, np.float64)
+    save("compressed_blocks", slots[bidx] * (col[None, :] < lens[bidx, None]))
+    if codec.ckpt_interval:
+        side = cb["sidecar"][: nb * codec.side_per_block]
+        sidx = pick(int(side.numel()), DUMP_SIDECAR)
+        w = side[sidx]
+        save("sidecar_lo32", w & 0xFFFFFFFF, np.float64)
+        save("sidecar_hi32", (w >> 32) & 0xFFFFFFFF, np.float64)
+
+
 def main():
     args = parse()
     self_launch(args)
@@ -584,6 +662,8 @@ def main():
           and bool(torch.equal(out, src)))
     comp_bytes = int(cb["comp_len"].to(torch.int64).sum())
     nb = codec.n_blocks(n)
+    if args.dump_outputs and rank == 0:  # before any side line reuses the buffers
+        dump_outputs(args.dump_outputs, codec, cb, out, dstat)
 
     def side_bytes_of(n_raw):  # sidecar bytes actually written/read for n_raw bytes of blocks
         if not args.ckpt:

@@ -163,7 +163,7 @@ def test_bench_c4_rehearsal_eight_ranks():
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FSEHIP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--strong", "--scheme", "round_robin",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "8", "--strong", "--scheme", "round_robin",
            "--bytes", str(512 << 20), "--steps", "2", "--warmup", "1", "--no-cpu", "--gather-timeout", "150"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=420)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -184,7 +184,7 @@ def _bench_two_ranks(extra_env, tmo="60"):
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, FSEHIP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", **extra_env)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
            "--bytes", str(8 * 65536 + 4321), "--no-cpu", "--gather-timeout", tmo]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=400)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -254,7 +254,7 @@ def test_bench_rccl_two_gpus():
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     env.pop("FSEHIP_BENCH_BACKEND", None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1",
            "--bytes", str(256 << 20), "--no-cpu", "--gather-timeout", "120"]
     r = subprocess.run(cmd, cwd=root, env=env, capture_output=True, text=True, timeout=400)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

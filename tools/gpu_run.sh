@@ -9,8 +9,8 @@
 # STEP:
 #   tests[:SEL]        pytest -m gpu over tests/ (or SEL: a file or -k expression)
 #   smoke              __graft_entry__.smoke()
-#   bench[:ARGS]       python3 bench.py ARGS (commas become spaces) -> bench_N.json
-#   prof[:ARGS]        rocprofv3 kernel trace + stats of bench.py --no-sweep --no-cpu
+#   bench[:ARGS]       python3 bench.py --full ARGS (commas become spaces) -> bench_N.json
+#   prof[:ARGS]        rocprofv3 kernel trace + stats of bench.py --full --no-sweep --no-cpu
 #                      --no-host-calls ARGS, the per-(kernel, grid) table
 #                      (tools/kernel_by_grid.py) and the fractions recomputed from
 #                      the trace (tools/frac_check.py)
@@ -50,12 +50,12 @@ for step in "$@"; do
       echo smoke-ok ;;
     bench)
       nb=$((nb + 1))
-      timeout -k 10 600 python3 bench.py ${arg//,/ } > "$O/bench_$nb.json" 2> "$O/bench_$nb.err" \
+      timeout -k 10 600 python3 bench.py --full ${arg//,/ } > "$O/bench_$nb.json" 2> "$O/bench_$nb.err" \
         || fail "$step" $? "$O/bench_$nb.err"
       tail -1 "$O/bench_$nb.json" | python3 tools/bench_brief.py ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof" -o bench -- \
-        python3 bench.py --no-sweep --no-cpu --no-host-calls ${arg//,/ } > "$O/bench_prof.json" 2> "$O/bench_prof.err" \
+        python3 bench.py --full --no-sweep --no-cpu --no-host-calls ${arg//,/ } > "$O/bench_prof.json" 2> "$O/bench_prof.err" \
         || fail "$step" $? "$O/bench_prof.err"
       python3 tools/kernel_by_grid.py "$O/prof/bench_kernel_trace.csv" > "$O/kernel_by_grid.txt"
       python3 tools/frac_check.py "$O/bench_prof.json" "$O/prof/bench_kernel_trace.csv" | tee "$O/frac_check.txt" ;;
