@@ -42,6 +42,7 @@ EXPORTS = (
     "bitstack_writer_new", "bitstack_writer_flush", "bitstack_writer_write_bits_raw",
     "bitstack_writer_write_bits_raw_unmasked", "bitstack_writer_write_bits", "bitstack_writer_write_bits_unmasked",
     "bitstack_writer_finish",
+    "fse_compress2_many", "fse_compress_many", "fsehip_compress_streams", "fsehip_stream_out_bytes",
 )
 
 STATUS = {
@@ -66,6 +67,11 @@ class Params(C.Structure):
     _fields_ = [("block_size", C.c_uint32), ("table_log", C.c_uint32),
                 ("ckpt_interval", C.c_uint32), ("max_table_log", C.c_uint32),
                 ("nstates", C.c_uint32)]
+
+
+class StreamDesc(C.Structure):
+    """fsehip_stream_desc: one stream of fsehip_compress_streams."""
+    _fields_ = [("src_off", C.c_uint64), ("out_off", C.c_uint64), ("src_len", C.c_uint32), ("out_cap", C.c_uint32)]
 
 
 class Histogram(C.Structure):
@@ -143,6 +149,11 @@ def load() -> C.CDLL:
     lib.fse_decompress.argtypes = [P, sz, P, sz, C.POINTER(sz)]
     lib.fse_decompress2_many.argtypes = [P, P, sz, P, sz, P, P]
     lib.fse_decompress_many.argtypes = [P, P, sz, P, sz, P, P]
+    lib.fse_compress2_many.argtypes = [P, P, sz, P, sz, P, P, P]
+    lib.fse_compress_many.argtypes = [P, P, sz, P, sz, P, P, P]
+    lib.fsehip_compress_streams.argtypes = [u32, u32, u32, P, P, u32, P, P, P, P, P]
+    lib.fsehip_stream_out_bytes.argtypes = [u32, u32]
+    lib.fsehip_stream_out_bytes.restype = u64
     lib.histogram_count.argtypes = [P, sz, P, C.POINTER(u32)]
     lib.fsehip_slot_bytes.argtypes = [u32, u32]
     lib.fsehip_slot_bytes.restype = u64

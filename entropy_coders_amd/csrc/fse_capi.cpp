@@ -459,6 +459,50 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
     return e == hipSuccess ? FSE_OK : FSE_ERR_HIP;
 }
 
+uint64_t fsehip_stream_out_bytes(uint32_t src_len, uint32_t max_table_log) {
+    const uint64_t L = max_table_log ? std::min<uint32_t>(max_table_log, 15u) : 12;
+    // as fsehip_slot_bytes: header <= 512 bytes, <= L bits per symbol, the
+    // final states and the marker; regions are 16-byte aligned, not 256
+    return round_up(512 + ((uint64_t)src_len * L + 2 * L + 1 + 7) / 8, 16);
+}
+
+int fsehip_compress_streams(uint32_t nstates, uint32_t table_log, uint32_t max_table_log, const uint8_t* d_src,
+                            const fsehip_stream_desc* d_desc, uint32_t n_streams, uint8_t* d_out,
+                            uint32_t* d_comp_len, uint32_t* d_payload_bits, int32_t* d_status,
+                            fsehip_stream_t stream) {
+    if (n_streams == 0) return FSE_OK;
+    if (nstates > 2 || !d_src || !d_desc || !d_out || !d_comp_len || !d_status ||
+        (reinterpret_cast<uintptr_t>(d_src) & 15u) || (reinterpret_cast<uintptr_t>(d_out) & 15u))
+        return FSE_ERR_BAD_ARG;
+    if (n_streams > (1u << 24) || max_table_log > 15) return FSE_ERR_UNSUPPORTED;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    if (table_log > 15) table_log = 15;  // Histogram::normalize clamps (histogram.rs:96)
+    if (table_log && table_log < 5) table_log = 5;
+    const fsehip_params p{0, table_log, 0, max_table_log, nstates};
+    const uint32_t lmax = kern_lmax(lmax_for(&p));
+    fsehip::EncParams P{};
+    P.nstates = nstates == 1 ? 1u : 2u;
+    P.src = d_src;
+    P.n_blocks = n_streams;
+    P.table_log = table_log;
+    P.out = d_out;
+    P.comp_len = d_comp_len;
+    P.payload_bits = d_payload_bits;
+    P.status = d_status;
+    P.lanes = 64;
+    P.desc = d_desc;
+    // L >= 13: the spread's symbols always in the workspace (a region may be
+    // far smaller than 512 + 2^L bytes); the lease is held until the launch
+    // is enqueued
+    std::unique_ptr<Lease> lease;
+    if (fsehip::enc_gsym(lmax)) {
+        lease = std::make_unique<Lease>(stream);
+        P.spread = static_cast<uint8_t*>(lease->get(SCRATCH_SPREAD, (uint64_t)n_streams << lmax));
+        if (!P.spread) return FSE_ERR_HIP;
+    }
+    return fsehip::launch_encode(P, lmax, static_cast<hipStream_t>(stream)) == hipSuccess ? FSE_OK : FSE_ERR_HIP;
+}
+
 // Sidecar-less decode at L <= 11 (both formats): the chains defer their symbols to
 // a map kernel when the stream's workspace can hold the state pairs (2 bytes
 // per output byte); without it the single-kernel serial decode runs.
@@ -1073,6 +1117,176 @@ int fse_decompress_many(const uint8_t* const* srcs, const size_t* src_lens, size
     return decompress_many(srcs, src_lens, n_streams, dst, dst_stride, dst_lens, statuses, 1);
 }
 
+// Many host buffers compressed in one call (lib.rs:146-183 / 112-143 per
+// buffer), the mirror image of decompress_many.  One batch: the buffers
+// idx[0..m) (each 0 < n <= kMaxBlock, non-null) packed back to back at
+// 16-byte aligned offsets behind their descriptors -- no common stride, and
+// no over-read allowance: the streams kernel reads exactly [src_off, src_off
+// + src_len) -- one copy in, fsehip_compress_streams into worst-case regions
+// (so the device never runs out of room and DST_TOO_SMALL is decided here
+// from the real length), the results compacted on the device
+// (stream_offsets_kernel + copy_blocks_kernel), the records and then the
+// compressed bytes copied back, and scattered to dst.
+extern "C++" {
+struct ManyRec {  // head of the device result buffer
+    uint64_t total;
+    uint64_t pad;
+};
+static std::atomic<uint64_t> g_compress_stage{kManyStage};
+}
+static int compress_batch(const uint8_t* const* srcs, const size_t* src_lens, const size_t* idx, size_t m,
+                          uint8_t* dst, size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits,
+                          int32_t* statuses, uint32_t nstates) {
+    // input staging: descriptors | output offsets (for the compaction) | sources
+    const uint64_t desc_bytes = round_up(sizeof(fsehip_stream_desc) * m, 256);
+    const uint64_t ooff_bytes = round_up(8ull * m, 256);
+    uint64_t in_total = 0, cap_total = 0;
+    for (size_t k = 0; k < m; ++k) {
+        in_total += round_up(src_lens[idx[k]], 16);
+        cap_total += fsehip_stream_out_bytes((uint32_t)src_lens[idx[k]], 11);
+    }
+    const uint64_t in_bytes = desc_bytes + ooff_bytes + in_total;
+    // result buffer: total | comp_len, payload_bits, status | packed offsets | packed streams
+    const uint64_t rec_bytes = round_up(sizeof(ManyRec) + 12ull * m, 256);
+    const uint64_t poff_bytes = round_up(8ull * m, 256);
+    uint8_t* h_in = g_pin.get(0, in_bytes);
+    uint8_t* d_in = g_stage.get(4, in_bytes);
+    uint8_t* d_reg = g_stage.get(5, cap_total);
+    uint8_t* d_res = g_stage.get(7, rec_bytes + poff_bytes + cap_total);
+    if (!h_in || !d_in || !d_reg || !d_res) return FSE_ERR_HIP;
+    fsehip_stream_desc* desc = reinterpret_cast<fsehip_stream_desc*>(h_in);
+    uint64_t* ooff = reinterpret_cast<uint64_t*>(h_in + desc_bytes);
+    uint64_t so = 0, oo = 0;
+    for (size_t k = 0; k < m; ++k) {
+        const uint32_t n = (uint32_t)src_lens[idx[k]];
+        const uint64_t cap = fsehip_stream_out_bytes(n, 11);
+        desc[k] = fsehip_stream_desc{so, oo, n, (uint32_t)cap};
+        ooff[k] = oo;
+        so += round_up(n, 16);
+        oo += cap;
+    }
+    uint8_t* h_src = h_in + desc_bytes + ooff_bytes;
+    for_streams(m, in_total, [&](size_t k) { memcpy(h_src + desc[k].src_off, srcs[idx[k]], desc[k].src_len); });
+    auto fail = [](int rc) {  // nothing may still read or write the pinned buffers
+        (void)hipStreamSynchronize(nullptr);
+        return rc;
+    };
+    if (hipMemcpyAsync(d_in, h_in, in_bytes, hipMemcpyHostToDevice, nullptr) != hipSuccess) return fail(FSE_ERR_HIP);
+    uint32_t* d_len = reinterpret_cast<uint32_t*>(d_res + sizeof(ManyRec));
+    uint32_t* d_bits = d_len + m;
+    int32_t* d_stat = reinterpret_cast<int32_t*>(d_bits + m);
+    uint64_t* d_poff = reinterpret_cast<uint64_t*>(d_res + rec_bytes);
+    uint8_t* d_packed = d_res + rec_bytes + poff_bytes;
+    int rc = fsehip_compress_streams(nstates, 0, 11, d_in + desc_bytes + ooff_bytes,
+                                     reinterpret_cast<const fsehip_stream_desc*>(d_in), (uint32_t)m, d_reg, d_len,
+                                     d_bits, d_stat, nullptr);
+    if (rc) return fail(rc);
+    if (fsehip::launch_stream_offsets(d_len, (uint32_t)m, d_poff, reinterpret_cast<uint64_t*>(d_res), nullptr) !=
+            hipSuccess ||
+        fsehip::launch_copy(d_reg, reinterpret_cast<const uint64_t*>(d_in + desc_bytes), d_len, (uint32_t)m, d_packed,
+                            d_poff, nullptr) != hipSuccess)
+        return fail(FSE_ERR_HIP);
+    uint8_t* h_rec = g_pin.get(1, rec_bytes);
+    if (!h_rec) return fail(FSE_ERR_HIP);
+    if (hipMemcpyAsync(h_rec, d_res, sizeof(ManyRec) + 12ull * m, hipMemcpyDeviceToHost, nullptr) != hipSuccess)
+        return fail(FSE_ERR_HIP);
+    if (hipStreamSynchronize(nullptr) != hipSuccess) return FSE_ERR_HIP;
+    // the records leave the pinned buffer before it may grow for the streams
+    std::vector<uint32_t> rec(3 * m);
+    const uint64_t total = reinterpret_cast<const ManyRec*>(h_rec)->total;
+    memcpy(rec.data(), h_rec + sizeof(ManyRec), 12ull * m);
+    const uint32_t *olen = rec.data(), *obits = olen + m;
+    const int32_t* ost = reinterpret_cast<const int32_t*>(obits + m);
+    if (total > cap_total) return FSE_ERR_HIP;
+    uint8_t* h_out = g_pin.get(1, std::max<uint64_t>(total, 16));
+    if (!h_out) return FSE_ERR_HIP;
+    if (total && hipMemcpy(h_out, d_packed, total, hipMemcpyDeviceToHost) != hipSuccess) return FSE_ERR_HIP;
+    std::vector<uint64_t> poff(m);
+    uint64_t po = 0;
+    for (size_t k = 0; k < m; ++k) {
+        poff[k] = po;
+        po += round_up(olen[k], 16);
+    }
+    for_streams(m, total, [&](size_t k) {
+        const size_t i = idx[k];
+        int32_t st = ost[k];
+        if (st == FSE_OK && olen[k] > dst_stride) st = FSE_ERR_DST_TOO_SMALL;
+        statuses[i] = st;
+        dst_lens[i] = st == FSE_OK ? olen[k] : 0;
+        if (payload_bits) payload_bits[i] = st == FSE_OK ? obits[k] : 0;
+        if (st == FSE_OK) memcpy(dst + i * dst_stride, h_out + poff[k], olen[k]);
+    });
+    return FSE_OK;
+}
+
+// A call of kCompressSingle buffers or fewer takes compress_one per buffer
+// (one wave and one synchronise each); larger calls the batch, in groups of
+// at most g_compress_stage bytes of staging each way.
+constexpr size_t kCompressSingle = 1;
+static int compress_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
+                         size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits, int32_t* statuses,
+                         uint32_t nstates) {
+    if (n_streams == 0) return FSE_OK;
+    if (!srcs || !src_lens || !dst || !dst_lens || !statuses || dst_stride == 0) return FSE_ERR_BAD_ARG;
+    if (n_streams > (1u << 24)) return FSE_ERR_UNSUPPORTED;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    const uint64_t stage = g_compress_stage.load(std::memory_order_relaxed);
+    std::vector<size_t> batch;
+    uint64_t in_b = 0, out_b = 0;
+    auto run = [&]() -> int {
+        if (batch.empty()) return FSE_OK;
+        int rc = FSE_OK;
+        if (n_streams <= kCompressSingle) {
+            for (size_t i : batch) {
+                size_t len = 0;
+                uint64_t bits = 0;
+                const int st = compress_one(srcs[i], src_lens[i], 0, dst + i * dst_stride, dst_stride, &len, &bits,
+                                            nstates);
+                if (st == FSE_ERR_HIP || st == FSE_ERR_NO_DEVICE) return st;
+                statuses[i] = st;
+                dst_lens[i] = st == FSE_OK ? len : 0;
+                if (payload_bits) payload_bits[i] = st == FSE_OK ? bits : 0;
+            }
+        } else {
+            rc = compress_batch(srcs, src_lens, batch.data(), batch.size(), dst, dst_stride, dst_lens, payload_bits,
+                                statuses, nstates);
+        }
+        batch.clear();
+        in_b = out_b = 0;
+        return rc;
+    };
+    for (size_t i = 0; i < n_streams; ++i) {
+        const size_t n = src_lens[i];
+        const int32_t st = n == 0 ? FSE_ERR_EMPTY  // size.ilog2() panics (histogram.rs:266)
+                           : !srcs[i] ? FSE_ERR_BAD_ARG
+                           : n > kMaxBlock ? FSE_ERR_UNSUPPORTED
+                                           : FSE_OK;
+        if (st != FSE_OK) {
+            statuses[i] = st;
+            dst_lens[i] = 0;
+            if (payload_bits) payload_bits[i] = 0;
+            continue;
+        }
+        const uint64_t a = round_up(n, 16) + sizeof(fsehip_stream_desc) + 8, o = fsehip_stream_out_bytes((uint32_t)n, 11) + 20;
+        if (!batch.empty() && (in_b + a > stage || out_b + o > stage))
+            if (int rc = run()) return rc;
+        batch.push_back(i);
+        in_b += a;
+        out_b += o;
+    }
+    return run();
+}
+
+int fse_compress2_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
+                       size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits, int32_t* statuses) {
+    return compress_many(srcs, src_lens, n_streams, dst, dst_stride, dst_lens, payload_bits, statuses, 2);
+}
+
+int fse_compress_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
+                      size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits, int32_t* statuses) {
+    return compress_many(srcs, src_lens, n_streams, dst, dst_stride, dst_lens, payload_bits, statuses, 1);
+}
+
 int histogram_count(const uint8_t* src, size_t n, uint32_t counts[256], uint32_t* table_len) {
     if (!counts) return FSE_ERR_BAD_ARG;
     if (n > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;  // histogram.rs:19 assert
@@ -1422,5 +1636,12 @@ int fsehip_rank_fallbacks(int device, uint32_t counts[3], int reset) {
 // fallback): -1 / 0 = atomic ranks checked per table (the default), 1 =
 // peer-mask ranks.  Returns the previous mode.
 int fsehipx_rank_mode(int mode) { return fsehip::rank_mode(mode < 0 ? -1 : mode > 0 ? 1 : 0); }
+
+// Tests only: the staging bytes per batch of fse_compress2_many /
+// fse_compress_many (0 = the product's 512 MiB), so that a test reaches the
+// split between batches with small inputs.  Returns the previous value.
+uint64_t fsehipx_compress_many_stage(uint64_t bytes) {
+    return g_compress_stage.exchange(bytes ? bytes : kManyStage, std::memory_order_relaxed);
+}
 
 }  // extern "C"

@@ -34,6 +34,17 @@ struct EncParams {
     // block b at spread + b * 2^LMAX, or (nullptr) in the block's own output
     // slot after its header words, when slot_bytes >= HDR_MAX + 2^LMAX
     uint8_t* spread;
+    // Streams form (encode_streams_kernel, launch_encode with desc != nullptr):
+    // stream b's source, length, output region and capacity come from
+    // desc[b] instead of block_size / n_total / slot_bytes (n_blocks = the
+    // number of streams; no sidecar).  Source reads: exactly the bytes
+    // [src_off, src_off + src_len) -- the histogram and the encode passes load
+    // 16-byte chunks only where a whole chunk lies inside the stream and read
+    // the rest bytewise -- so src + src_off must be 16-byte aligned and nothing
+    // past src_len need be readable.  Stores: only inside
+    // [out_off, out_off + out_cap), out + out_off 16-byte aligned.  At
+    // L >= 13 `spread` is required (a region is never used as scratch).
+    const fsehip_stream_desc* desc;
 };
 // Encoder kernels whose spread symbol array lives in global memory (L >= 13):
 // their LDS then fits 7 / 4 / 2 workgroups per CU at L = 13 / 14 / 15
@@ -178,5 +189,10 @@ hipError_t launch_pack(const uint8_t* slots, uint64_t slot_bytes, const uint32_t
                        uint32_t n_blocks, uint8_t* stream, int unpack, hipStream_t hs);
 hipError_t launch_copy(const uint8_t* src, const uint64_t* src_off, const uint32_t* lens, uint32_t n_blocks,
                        uint8_t* dst, const uint64_t* dst_off, hipStream_t hs);
+
+// Packed offsets of a batch of compressed streams (each length rounded up to
+// 16 bytes) and their total, for launch_copy and the copy to the host.
+hipError_t launch_stream_offsets(const uint32_t* lens, uint32_t n, uint64_t* offsets, uint64_t* total,
+                                 hipStream_t hs);
 
 }  // namespace fsehip

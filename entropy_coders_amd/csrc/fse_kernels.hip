@@ -636,10 +636,40 @@ struct EncSmem {
     }
 };
 
-template <int LMAX, int T, int NS>
-__global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
+// Where a block's bytes come from and go to.  Blocks: equal pieces of one
+// buffer into equal slots (worst-case sized).  Streams: a descriptor per
+// stream (EncParams::desc); `pre` is the status of a descriptor the kernel
+// refuses before it touches memory (misaligned offsets, a length above 2^28).
+struct EncGeom {
+    const uint8_t* blk;
+    uint32_t n;
+    uint8_t* out;
+    uint64_t cap;  // bytes of the output slot / region
+    int pre;
+};
+template <bool STREAMS>
+__device__ __forceinline__ EncGeom enc_geom(const EncParams& P, uint64_t gb) {
+    if constexpr (STREAMS) {
+        const fsehip_stream_desc d = P.desc[gb];
+        const int pre = ((d.src_off | d.out_off) & 15u) ? FSE_ERR_BAD_ARG
+                        : d.src_len > (1u << 28)        ? FSE_ERR_UNSUPPORTED
+                                                        : FSE_OK;
+        return EncGeom{P.src + d.src_off, pre == FSE_OK ? d.src_len : 0u, P.out + d.out_off, d.out_cap, pre};
+    } else {
+        const uint64_t off = gb * P.block_size;
+        return EncGeom{P.src + off, (uint32_t)min((uint64_t)P.block_size, P.n_total - off), P.out + gb * P.slot_bytes,
+                       P.slot_bytes, FSE_OK};
+    }
+}
+
+// The encoder of one workgroup: encode_blocks_kernel (STREAMS = false) and
+// encode_streams_kernel (true) differ in enc_geom and in what follows from a
+// region that is not worst-case sized: no header store before the capacity is
+// known to hold it, no scratch inside the region, and the region's last
+// partial word stored bytewise.
+template <int LMAX, int T, int NS, bool STREAMS>
+__device__ __forceinline__ void encode_body(const EncParams& P, EncSmem<LMAX, T>& sm) {
     constexpr int BPW = 64 / T;
-    __shared__ EncSmem<LMAX, T> sm;
     // the tail in phase 2's trajectory struct must sit above every phase-1 byte
     static_assert(!EncSmem<LMAX, T>::TAIL_IN_P2 ||
                       64u * track_slots<LMAX>() * 12u + 4u * (T + 1u) >= sizeof(sm.ph.p1),
@@ -656,9 +686,9 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
             if (lane == 0) sm.tail().status[b] = 1;  // no block
             continue;
         }
-        const uint64_t off = gb * P.block_size;
-        const uint32_t n = (uint32_t)min((uint64_t)P.block_size, P.n_total - off);
-        const uint8_t* blk = P.src + off;
+        const EncGeom G = enc_geom<STREAMS>(P, gb);
+        const uint32_t n = G.n;
+        const uint8_t* blk = G.blk;
         uint32_t* counts = sm.ph.p1.cnt;  // the spread reuses cnt[] after normalize
         using Sm = EncSmem<LMAX, T>;
         const uint32_t tl = wave_histogram<Sm::HS>(
@@ -668,9 +698,9 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
             if (lane == 0) P.status[gb] = (int32_t)tl;
             continue;
         }
-        int rc = FSE_OK;
+        int rc = G.pre;
         uint32_t Lreq = P.table_log, L = 0, slow = 0;
-        if (n == 0) rc = FSE_ERR_EMPTY;
+        if (rc == FSE_OK && n == 0) rc = FSE_ERR_EMPTY;
         if (rc == FSE_OK && P.table_log == 0) rc = optimal_log2(n, tl, &Lreq);  // histogram.rs:301
         if (rc == FSE_OK) rc = wave_normalize(counts, n, tl, Lreq, sm.ph.p1.norm, &L, &slow, sm.tail().scratch);
         if (rc == FSE_OK && n < 2) rc = FSE_ERR_TOO_SHORT;  // lib.rs:154/156 unwrap
@@ -683,10 +713,13 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
                 rc = hl;
             } else {
                 // whole header words go to the slot now (no payload store
-                // touches them); the last partial word is merged at the end
+                // touches them); the last partial word is merged at the end.
+                // (Streams: a region too small for the header stays
+                // untouched; `fits` fails for it in phase 2.)
                 const uint32_t* h = sm.ph.p1.u.hdrw;
-                uint32_t* gw = reinterpret_cast<uint32_t*>(P.out + gb * P.slot_bytes);
-                for (uint32_t w = lane; w < (uint32_t)hl / 4u; w += WAVE) gw[w] = h[w];
+                uint32_t* gw = reinterpret_cast<uint32_t*>(G.out);
+                if (!STREAMS || (uint64_t)hl <= G.cap)
+                    for (uint32_t w = lane; w < (uint32_t)hl / 4u; w += WAVE) gw[w] = h[w];
                 if (lane == 0) sm.tail().hv[b] = (hl & 3) ? h[hl / 4] & ((1u << (8u * (hl & 3))) - 1u) : 0u;
             }
             wave_sync();  // the spread reuses the header's LDS
@@ -698,8 +731,8 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
             const uint16_t* cumul = sm.ph.p1.cumul;
             constexpr bool GSYM = enc_gsym(LMAX);
             uint8_t* const sym_at = !GSYM ? sm.ph.p1.u.sym_at
-                                    : P.spread ? P.spread + gb * (uint64_t)(1u << LMAX)
-                                               : P.out + gb * P.slot_bytes + ENC_SPREAD_OFF;
+                                    : (STREAMS || P.spread) ? P.spread + gb * (uint64_t)(1u << LMAX)
+                                                            : G.out + ENC_SPREAD_OFF;
             static_assert(ENC_SPREAD_OFF >= HDR_MAX && ENC_SPREAD_OFF % 16u == 0u, "in-slot spread array");
             rc = wave_build_spread<64, false, GSYM>(sm.ph.p1.norm, L, tl, sym_at, reinterpret_cast<uint8_t*>(st), sm.ph.p1.cumul,
                                    sm.ph.p1.cnt,
@@ -776,9 +809,9 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
     using Sm2 = EncSmem<LMAX, T>;
     const uint32_t hl_early = Sm2::TAIL_IN_P2 ? sm.tail().hl[b] : 0u;
     const uint32_t hv_early = Sm2::TAIL_IN_P2 ? sm.tail().hv[b] : 0u;
-    const uint64_t boff = gb * P.block_size;
-    const uint32_t n = live ? (uint32_t)min((uint64_t)P.block_size, P.n_total - boff) : 0u;
-    const uint8_t* blk = P.src + boff;
+    const EncGeom G = live ? enc_geom<STREAMS>(P, gb) : EncGeom{P.src, 0u, P.out, 0u, FSE_OK};
+    const uint32_t n = G.n;
+    const uint8_t* blk = G.blk;
     const uint32_t L = sm.tail().L[b];
     const EncTab tab{sm.tt[b]};
     // main-loop steps: pairs (NS = 2) or symbols below the seed (NS = 1)
@@ -872,14 +905,15 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
     }
     const uint32_t total_bits = hdr_bits + __shfl(suffix, 0, T);
     const uint32_t off = hdr_bits + suffix - mybits;
-    const bool fits = (uint64_t)total_bits <= P.slot_bytes * 8ull && !FSE_ABLATE(P, 2u);
-    uint32_t* gw = reinterpret_cast<uint32_t*>(P.out + gb * P.slot_bytes);
+    const bool fits = (uint64_t)total_bits <= G.cap * 8ull && !FSE_ABLATE(P, 2u);
+    uint32_t* gw = reinterpret_cast<uint32_t*>(G.out);
+    const uint32_t wlim = (uint32_t)(G.cap >> 2);  // whole words of the slot / region
 
     // emit pass (its ring overlays the trajectories and end states: every
     // lane is past the repair rounds here)
     ENC_SYNC();
     if (act && fits) {
-        em.start(gw, off, FSE_ABLATE(P, 4u) ? 0u : (uint32_t)(P.slot_bytes >> 2),  // debug bit 2: no payload stores (ablation)
+        em.start(gw, off, FSE_ABLATE(P, 4u) ? 0u : wlim,  // debug bit 2: no payload stores (ablation)
                  &sm.ph.p2.ring[lane * RING_STRIDE]);
         {
             if (P.sidecar && P.ckpt_interval) {
@@ -961,7 +995,14 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
                 if (wq != w) break;
                 v |= sm.ph.p2.mg.mval[b][q];
             }
-            if (w < (uint32_t)(P.slot_bytes >> 2)) gw[w] = v;
+            if (w < wlim) {
+                gw[w] = v;
+            } else if (STREAMS && w == wlim) {
+                // the region's last, partial word (out_cap % 4 bytes of it):
+                // complete words lie below wlim when the stream fits, so only
+                // a merged boundary word can land here
+                for (uint32_t i = 0; i < ((uint32_t)G.cap & 3u); ++i) G.out[4ull * w + i] = (uint8_t)(v >> (8u * i));
+            }
         }
     }
     FSE_STAMP(P, 8);
@@ -979,6 +1020,18 @@ __global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
 
 #undef ENC_SYNC
 #undef ENC_WGID
+
+template <int LMAX, int T, int NS>
+__global__ __launch_bounds__(64) void encode_blocks_kernel(EncParams P) {
+    __shared__ EncSmem<LMAX, T> sm;
+    encode_body<LMAX, T, NS, false>(P, sm);
+}
+// One stream per wave (T = 64), geometry from EncParams::desc.
+template <int LMAX, int T, int NS>
+__global__ __launch_bounds__(64) void encode_streams_kernel(EncParams P) {
+    __shared__ EncSmem<LMAX, T> sm;
+    encode_body<LMAX, T, NS, true>(P, sm);
+}
 
 // ------------------------------------------------------------------------
 // Histogram::new per block (histogram::count), one wave per block.
@@ -1075,6 +1128,39 @@ __global__ __launch_bounds__(256) void copy_blocks_kernel(const uint8_t* __restr
 }
 
 // ------------------------------------------------------------------------
+// Packed layout of a batch of compressed streams on their way to the host:
+// offsets[i] = the exclusive sum of the lengths before i, each rounded up to
+// 16 bytes (aligned copies on both sides of the bus), total = their sum.
+// One workgroup: a contiguous run of streams per thread, the runs' sums
+// scanned in LDS.
+// ------------------------------------------------------------------------
+__global__ __launch_bounds__(1024) void stream_offsets_kernel(const uint32_t* __restrict__ lens, uint32_t n,
+                                                              uint64_t* __restrict__ offsets,
+                                                              uint64_t* __restrict__ total) {
+    __shared__ uint64_t part[1024];
+    const uint32_t t = threadIdx.x;
+    const uint32_t per = (n + 1023u) / 1024u;
+    const uint32_t lo = (uint32_t)min((uint64_t)t * per, (uint64_t)n), hi = (uint32_t)min((uint64_t)lo + per, (uint64_t)n);
+    auto r16 = [](uint32_t x) { return ((uint64_t)x + 15u) & ~15ull; };
+    uint64_t s = 0;
+    for (uint32_t i = lo; i < hi; ++i) s += r16(lens[i]);
+    part[t] = s;
+    __syncthreads();
+    for (uint32_t d = 1; d < 1024u; d <<= 1) {
+        const uint64_t v = t >= d ? part[t - d] : 0ull;
+        __syncthreads();
+        part[t] += v;
+        __syncthreads();
+    }
+    uint64_t o = part[t] - s;
+    for (uint32_t i = lo; i < hi; ++i) {
+        offsets[i] = o;
+        o += r16(lens[i]);
+    }
+    if (t == 1023u) *total = part[1023];
+}
+
+// ------------------------------------------------------------------------
 // Synthetic generator (same definition as oracle fo_generate).
 // ------------------------------------------------------------------------
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
@@ -1131,6 +1217,35 @@ hipError_t launch_encode(const EncParams& P0, uint32_t lmax, hipStream_t stream)
     const uint32_t bpw = 64u / T;
     const dim3 g((P.n_blocks + bpw - 1u) / bpw), b(64);
     auto go = [&](auto kern, uint32_t pad = 0) { hipLaunchKernelGGL(kern, g, b, P.xlds ? P.xlds : pad, stream, P); };
+    if (P.desc) {
+        // streams form: one stream per wave, by table-log class as below
+        if (enc_gsym(lmax) && !P.spread) return hipErrorInvalidValue;
+        const dim3 gs(P.n_blocks);
+        auto gos = [&](auto kern, uint32_t pad = 0) { hipLaunchKernelGGL(kern, gs, b, pad, stream, P); };
+        if (P.nstates == 1) {
+            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 1>);
+            else if (lmax <= 12) gos(encode_streams_kernel<12, 64, 1>);
+            else if (lmax <= 13) gos(encode_streams_kernel<13, 64, 1>);
+            else if (lmax <= 14) gos(encode_streams_kernel<14, 64, 1>);
+            else gos(encode_streams_kernel<15, 64, 1>);
+        } else {
+            // the same 11 workgroups per CU as the block kernel (pad11 below)
+            static const uint32_t pad11s = [] {
+                hipFuncAttributes fa{};
+                if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(encode_streams_kernel<11, 64, 2>)) !=
+                    hipSuccess)
+                    return 0u;
+                const size_t per = (160u << 10) / ENC_WGS - 64u;
+                return fa.sharedSizeBytes < per ? (uint32_t)(per - fa.sharedSizeBytes) : 0u;
+            }();
+            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 2>, pad11s);
+            else if (lmax <= 12) gos(encode_streams_kernel<12, 64, 2>);
+            else if (lmax <= 13) gos(encode_streams_kernel<13, 64, 2>);
+            else if (lmax <= 14) gos(encode_streams_kernel<14, 64, 2>);
+            else gos(encode_streams_kernel<15, 64, 2>);
+        }
+        return hipGetLastError();
+    }
     if (P.nstates == 1) {  // fse_compress (lib.rs:112-143)
         if (lmax <= 11) go(encode_blocks_kernel<11, 64, 1>);
         else if (lmax <= 12) go(encode_blocks_kernel<12, 64, 1>);
@@ -1196,6 +1311,12 @@ hipError_t launch_copy(const uint8_t* src, const uint64_t* src_off, const uint32
                        uint8_t* dst, const uint64_t* dst_off, hipStream_t hs) {
     hipLaunchKernelGGL(copy_blocks_kernel, dim3(n_blocks), dim3(256), 0, hs, src, src_off, lens, n_blocks, dst,
                        dst_off);
+    return hipGetLastError();
+}
+
+hipError_t launch_stream_offsets(const uint32_t* lens, uint32_t n, uint64_t* offsets, uint64_t* total,
+                                 hipStream_t hs) {
+    hipLaunchKernelGGL(stream_offsets_kernel, dim3(1), dim3(1024), 0, hs, lens, n, offsets, total);
     return hipGetLastError();
 }
 

@@ -161,6 +161,92 @@ def decompress_streams(streams, out_stride: int, nstates: int = 2, max_table_log
             STATUS.get(int(st[i]), str(int(st[i]))) for i in range(len(streams))]
 
 
+def compress2_many(buffers, nstates: int = 2, dst_stride=None, raw: bool = False, dst=None):
+    """`fse_compress2_many` / `fse_compress_many` (nstates 1): many host
+    buffers of any lengths in one call, each compressed as `fse_compress2`
+    (lib.rs:146) would into an empty buffer of dst_stride bytes (default: a
+    capacity that holds the longest).  Returns a list with, per buffer,
+    (bytes, payload bits) or the name of its status; with raw=True the call's
+    own outputs instead: (dst, lengths, payload bits, statuses) as numpy
+    arrays (dst may be passed in, n * dst_stride bytes).  An entry of
+    `buffers` may be (None, n): a null pointer of length n."""
+    from ._lib import STATUS
+
+    if nstates not in (1, 2):
+        raise ValueError(f"nstates must be 1 or 2, not {nstates!r}")
+    lib = load()
+    null = [isinstance(x, tuple) and x[0] is None for x in buffers]
+    bufs = [np.empty(0, dtype=np.uint8) if z else _buf(x) for x, z in zip(buffers, null)]
+    n = len(bufs)
+    ptrs = np.array([b.ctypes.data if len(b) else 0 for b in bufs] or [0], dtype=np.uintp)
+    lens = np.array([int(x[1]) if z else len(b) for x, b, z in zip(buffers, bufs, null)] or [0], dtype=np.uintp)
+    if dst_stride is None:
+        dst_stride = int(lib.fsehip_stream_out_bytes(int(lens.max()) if n else 0, 11))
+    if dst is None:
+        dst = np.zeros(max(n, 1) * dst_stride, dtype=np.uint8)
+    elif not (isinstance(dst, np.ndarray) and dst.dtype == np.uint8 and dst.flags.c_contiguous
+              and dst.flags.writeable and dst.nbytes >= n * dst_stride):
+        raise ValueError(f"dst must be a writeable C-contiguous uint8 ndarray of >= {n * dst_stride} bytes")
+    out_lens = np.zeros(max(n, 1), dtype=np.uintp)
+    bits = np.zeros(max(n, 1), dtype=np.uint64)
+    st = np.zeros(max(n, 1), dtype=np.int32)
+    fn = lib.fse_compress2_many if nstates == 2 else lib.fse_compress_many
+    check(fn(_p(ptrs), _p(lens), n, _p(dst), dst_stride, _p(out_lens), _p(bits), _p(st)), "fse_compress2_many")
+    if raw:
+        return dst, out_lens[:n], bits[:n], st[:n]
+    return [(dst[i * dst_stride: i * dst_stride + int(out_lens[i])].tobytes(), int(bits[i])) if st[i] == 0 else
+            STATUS.get(int(st[i]), str(int(st[i]))) for i in range(n)]
+
+
+def compress_streams(buffers, nstates: int = 2, table_log: int = 0, device=None, out_caps=None, max_table_log: int = 0,
+                     raw: bool = False):
+    """`fsehip_compress_streams`: many inputs of any lengths compressed at once
+    on the GPU, each as `fse_compress2` (nstates 2) / `fse_compress` (1) would
+    -- with table_log as `fse_compress2_log`.  The inputs are laid out back to
+    back at 16-byte aligned offsets; each output region has out_caps[i] bytes
+    (default `fsehip_stream_out_bytes`) and the regions are 64 bytes apart,
+    the gaps filled with 0xA5.  Returns a list with, per stream, (bytes,
+    payload bits) or the name of its status; with raw=True (statuses, lengths,
+    payload bits, out bytes as numpy, descriptors) for bounds checks."""
+    import torch
+
+    from ._lib import STATUS, StreamDesc
+
+    lib = load()
+    dev = torch.device(device or "cuda")
+    bufs = [_buf(x) for x in buffers]
+    n = len(bufs)
+    lmax = max_table_log or (max(11, min(table_log, 15)) if table_log else 11)
+    caps = [int(lib.fsehip_stream_out_bytes(len(b), lmax)) for b in bufs] if out_caps is None else list(out_caps)
+    desc = (StreamDesc * max(n, 1))()
+    so = oo = 0
+    for i, b in enumerate(bufs):
+        desc[i] = StreamDesc(so, oo, len(b), caps[i])
+        so += (len(b) + 15) // 16 * 16
+        oo += (caps[i] + 15) // 16 * 16 + 64
+    host = np.zeros(max(so, 16), dtype=np.uint8)
+    for i, b in enumerate(bufs):
+        host[desc[i].src_off: desc[i].src_off + len(b)] = b
+    d_src = torch.from_numpy(host).to(dev)
+    d_desc = torch.from_numpy(np.frombuffer(bytes(desc), dtype=np.uint8).copy()).to(dev)
+    out = torch.full((max(oo, 16),), 0xA5, dtype=torch.uint8, device=dev)
+    comp_len = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    bits = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=dev)
+    check(lib.fsehip_compress_streams(nstates, table_log, max_table_log, C.c_void_p(d_src.data_ptr()),
+                                      C.c_void_p(d_desc.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                      C.c_void_p(comp_len.data_ptr()), C.c_void_p(bits.data_ptr()),
+                                      C.c_void_p(status.data_ptr()),
+                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+          "fsehip_compress_streams")
+    torch.cuda.synchronize(dev)
+    ho, cl, pb, st = out.cpu().numpy(), comp_len.cpu().numpy()[:n], bits.cpu().numpy()[:n], status.cpu().numpy()[:n]
+    if raw:
+        return st, cl, pb, ho, [(d.src_off, d.out_off, d.src_len, d.out_cap) for d in desc[:n]]
+    return [(ho[desc[i].out_off: desc[i].out_off + int(cl[i])].tobytes(), int(pb[i]) & 0xFFFFFFFF) if st[i] == 0 else
+            STATUS.get(int(st[i]), str(int(st[i]))) for i in range(n)]
+
+
 def histogram_count(src) -> tuple[np.ndarray, int]:
     """`Histogram::new(data)` (histogram.rs:18-66): (counts[256], table_len)."""
     a = _buf(src)
@@ -580,7 +666,7 @@ class BlockCodec:
 
 __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStackWriter", "BitStreamReader", "BlockCodec", "DecodeTable", "EncodeTable", "FseError",
            "Histogram", "NormHistogram", "bitstack_read", "bitstack_write", "bitstream_read", "compress", "compress2",
-           "compress2_log", "compress_nh", "decode_table_new", "decompress", "decompress2", "decompress2_many",
+           "compress2_log", "compress2_many", "compress_nh", "compress_streams", "decode_table_new", "decompress", "decompress2", "decompress2_many",
            "decompress_streams",
            "encode_table_new",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",

@@ -110,6 +110,46 @@ int fse_decompress2_many(const uint8_t* const* srcs, const size_t* src_lens, siz
 int fse_decompress_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
                         size_t dst_stride, size_t* dst_lens, int32_t* statuses);
 
+/* Many fse_compress2 / fse_compress calls in one (lib.rs:146-183 / 112-143
+ * per buffer): the drop-in for a caller's loop over many records, columns or
+ * messages, and the mirror image of fse_decompress2_many.  Buffer i
+ * (srcs[i], src_lens[i] bytes, any lengths) is compressed into
+ * dst + i * dst_stride, at most dst_stride bytes (it does not append);
+ * dst_lens[i], payload_bits[i] (may be NULL) and statuses[i] are what
+ * fse_compress2(srcs[i], ...) gives into an empty buffer of dst_stride bytes:
+ * EMPTY for a zero length, TOO_SHORT, ALL_ZERO_SYMBOL0, UNSUPPORTED above
+ * 2^28 bytes, BAD_ARG for a null srcs[i] with a non-zero length, and
+ * DST_TOO_SMALL exactly when the compressed length exceeds dst_stride (the
+ * device compresses into worst-case regions, so the length is always known);
+ * dst_lens[i] = 0 for every failed buffer, and no byte of dst outside a
+ * buffer's own first dst_lens[i] bytes is written.  Returns FSE_OK when the
+ * batch ran (look at statuses), or a call-level error (BAD_ARG: a null array
+ * or dst_stride == 0; UNSUPPORTED: more than 2^24 buffers; NO_DEVICE, HIP).
+ *
+ * The inputs are packed back to back (16-byte aligned, no common stride: one
+ * long buffer does not multiply the staging of the short ones) with their
+ * descriptors in pinned memory and go to the device in one copy;
+ * fsehip_compress_streams encodes one buffer per wave; the results are
+ * compacted on the device, so the copy back carries the compressed bytes
+ * (each rounded up to 16) and 12 bytes per buffer, not the capacities.  Calls
+ * are split into batches of at most 512 MiB of staging each way; where the
+ * split falls does not show in the results.  Synchronous on the default
+ * stream; staging buffers per thread (grow-only, fsehip_release_workspace).
+ *
+ * Where the GPU pays (MI355X, 64 KiB C2 buffers, host buffers in and out,
+ * PCIe included; tools/many_compress.py, profiles/many_compress/): 0.212 ms
+ * for 2 buffers, 0.218 for 3, 0.272 for 16, 1.41 for 256, 4.09 for 1,000
+ * (14.9 GiB/s), 14.1 for 4,000 (17.4 GiB/s); 1,000 buffers of 4 KiB 0.41 ms,
+ * 16,000 4.04 ms -- against 0.17-0.19 ms per buffer for a loop of
+ * fse_compress2 calls (55 us at 4 KiB) and 0.41 ms per buffer on one host
+ * core.  Crossover: the batch wins from two buffers on (0.212 against 0.352
+ * ms); one buffer through the batch costs 0.209 ms against the single call's
+ * 0.185, so a call of one buffer takes the single call's path. */
+int fse_compress2_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
+                       size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits, int32_t* statuses);
+int fse_compress_many(const uint8_t* const* srcs, const size_t* src_lens, size_t n_streams, uint8_t* dst,
+                      size_t dst_stride, size_t* dst_lens, uint64_t* payload_bits, int32_t* statuses);
+
 /* Replaces `Histogram::new(data)` (histogram.rs:18-66) -- the north star's
  * `histogram::count`: counts[256], table_len = 1 + largest symbol. */
 int histogram_count(const uint8_t* src, size_t n, uint32_t counts[256], uint32_t* table_len);
@@ -360,7 +400,9 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
  *                  decode without retrying) until the next release;
  *   encode spread  2^L bytes per block (L the encode kernel's table log,
  *                  13..15) when the slots are smaller than 512 + 2^L bytes
- *                  (fsehip_compress_blocks);
+ *                  (fsehip_compress_blocks), and always 2^L bytes per stream
+ *                  in fsehip_compress_streams (a stream's output region is
+ *                  never scratch);
  *   header parse   520 bytes per block (the headers parsed one per lane
  *                  before the table build: batches of >= 256 blocks at
  *                  max_table_log <= 12, fsehip_build_dtables included;
@@ -430,6 +472,58 @@ int fsehip_build_sidecar(const fsehip_params* p, const uint8_t* d_in, uint64_t s
 int fsehip_decompress_streams(uint32_t nstates, uint32_t max_table_log, const uint8_t* d_in, uint64_t in_stride,
                               const uint32_t* d_comp_len, uint32_t n_streams, uint8_t* d_out, uint32_t out_stride,
                               uint32_t* d_out_len, int32_t* d_status, fsehip_stream_t stream);
+
+/* Batched fse_compress2 / fse_compress (nstates 2 or 0 / 1) of n_streams
+ * independent inputs of any lengths: the compress side of
+ * fsehip_decompress_streams.  Stream i is the src_len bytes at
+ * d_src + src_off; its header||payload goes to d_out + out_off, at most
+ * out_cap bytes, and is byte for byte what fse_compress2 / fse_compress
+ * produce for that input -- with table_log != 0 what fse_compress2_log does
+ * (Histogram::normalize(table_log), clamped to 5..15); table_log 0 picks
+ * each stream's own optimal_log2.  max_table_log bounds the table log of the
+ * kernels as in fsehip_params (0 = derive: 11, or table_log above it).
+ *
+ * d_comp_len[i], d_payload_bits[i] (may be NULL) and d_status[i] are the
+ * single call's: EMPTY, TOO_SHORT, ALL_ZERO_SYMBOL0, CURSED, BAD_TABLE and
+ * ENCODER_INIT in the same cases; UNSUPPORTED for src_len above 2^28 or a
+ * table log above the kernel bound; DST_TOO_SMALL when the stream does not
+ * fit out_cap; BAD_ARG when src_off or out_off is not a multiple of 16.
+ * d_comp_len[i] = 0 for every stream that failed.
+ *
+ * Memory rules.  Reads: exactly [src_off, src_off + src_len) of each stream
+ * (16-byte loads only where a whole aligned chunk lies inside the stream, the
+ * rest bytewise), so nothing past src_len need be readable; d_src itself
+ * 16-byte aligned.  Stores: only inside [out_off, out_off + out_cap), whatever
+ * the status (a region too small for the header stays untouched; bytes of a
+ * region beyond d_comp_len[i] are unspecified); d_out 16-byte aligned.
+ * Regions must not overlap.  fsehip_stream_out_bytes(src_len, max_table_log)
+ * is a capacity that always suffices.  There is no sidecar: the streams
+ * decode with fsehip_decompress_streams.
+ *
+ * Workspace: at kernel table logs 13..15 the spread's 2^L-byte symbol array
+ * of every stream is leased from the stream's workspace (n_streams << L
+ * bytes, the encode-spread entry of the workspace note at
+ * fsehip_decompress_blocks) -- a stream's output region is never used as
+ * scratch, whatever its capacity.
+ *
+ * Asynchronous on `stream`.  n_streams == 0 returns FSE_OK and does
+ * nothing; a null pointer, nstates > 2 or a misaligned d_src / d_out is
+ * BAD_ARG, n_streams > 2^24 or max_table_log > 15 UNSUPPORTED, before any
+ * device use; otherwise NO_DEVICE or HIP. */
+typedef struct {
+    uint64_t src_off; /* byte offset of the stream in d_src, a multiple of 16 */
+    uint64_t out_off; /* byte offset of its output region in d_out, a multiple of 16 */
+    uint32_t src_len; /* bytes, <= 2^28 */
+    uint32_t out_cap; /* bytes of the output region (any value) */
+} fsehip_stream_desc;
+int fsehip_compress_streams(uint32_t nstates, uint32_t table_log, uint32_t max_table_log, const uint8_t* d_src,
+                            const fsehip_stream_desc* d_desc, uint32_t n_streams, uint8_t* d_out,
+                            uint32_t* d_comp_len, uint32_t* d_payload_bits, int32_t* d_status,
+                            fsehip_stream_t stream);
+/* Output capacity that holds any stream of src_len bytes at table logs <=
+ * max_table_log (0 = 12): 512 header bytes + src_len * L + 2 L + 1 bits,
+ * rounded up to 16 bytes. */
+uint64_t fsehip_stream_out_bytes(uint32_t src_len, uint32_t max_table_log);
 
 /* Free the workspace of (device, stream) -- device < 0: of every device for
  * that stream handle -- after the work already enqueued on the stream, plus
