@@ -1077,7 +1077,9 @@ __global__ __launch_bounds__(256) void pack_blocks_kernel(const uint8_t* __restr
             for (uint64_t d = d0 + threadIdx.x; d < d1; d += 256u) {
                 const uint32_t sb = head + 4u * (uint32_t)(d - d0);  // slot byte offset
                 const uint32_t q = sb >> 2, sh = sb & 3u;
-                const uint32_t lo = src[q], hi = src[q + 1u];  // slot slack covers q + 1
+                // the word above is read only when it carries bytes of this
+                // block: no read beyond roundup(len, 4)
+                const uint32_t lo = src[q], hi = sh ? src[q + 1u] : 0u;
                 dst[d] = __builtin_amdgcn_alignbyte(hi, lo, sh);
             }
         }

@@ -534,7 +534,18 @@ int fsehip_release_workspace(int device, fsehip_stream_t stream);
 
 /* Compact the slot layout into one stream (blocks back to back at the byte
  * offsets d_offsets[b], an exclusive scan of d_comp_len) and back.  Used to
- * ship compressed shards between GPUs (RCCL gather) or to the host. */
+ * ship compressed shards between GPUs (RCCL gather) or to the host.
+ * Block b is the first d_comp_len[b] bytes of the slot at d_slots +
+ * b * slot_bytes (slot_bytes a multiple of 16; d_slots and d_stream 4-byte
+ * aligned, as device allocations are).
+ *  fsehip_pack_blocks stores exactly the bytes [d_offsets[b], d_offsets[b] +
+ *    d_comp_len[b]) of d_stream, whatever their alignment (a dword shared by
+ *    two blocks is written bytewise by each), and reads each slot in whole
+ *    dwords: up to roundup(d_comp_len[b], 4) bytes of it, never more.
+ *  fsehip_unpack_blocks stores exactly the first d_comp_len[b] bytes of each
+ *    slot (the rest of the slot keeps what it held) and reads exactly the
+ *    block's bytes of d_stream.
+ * n_blocks == 0 returns FSE_OK and does nothing. */
 
 int fsehip_pack_blocks(const uint8_t* d_slots, uint64_t slot_bytes, const uint32_t* d_comp_len,
                        const uint64_t* d_offsets, uint32_t n_blocks, uint8_t* d_stream, fsehip_stream_t stream);
@@ -544,7 +555,15 @@ int fsehip_unpack_blocks(const uint8_t* d_stream, const uint64_t* d_offsets, con
 /* Move whole blocks between packed streams: block b's d_lens[b] bytes go from
  * d_src + d_src_offsets[b] to d_dst + d_dst_offsets[b] (any byte offsets;
  * ranges must not overlap).  Selects one rank's blocks out of a packed
- * stream for the distributed scatter (entropy_coders_amd/dist.py). */
+ * stream for the distributed scatter (entropy_coders_amd/dist.py).
+ * d_src and d_dst themselves may have any alignment as well: the kernel
+ * counts its dwords from them, and global memory on gfx950 takes the
+ * unaligned dword accesses this gives.  Stores: exactly the bytes of each
+ * destination range (a dword shared by two blocks is written bytewise by
+ * each).  Reads: the whole dwords, counted from d_src, that hold a byte of
+ * the block: never below d_src, and at most up to d_src +
+ * roundup(d_src_offsets[b] + d_lens[b], 4), which must be readable.
+ * n_blocks == 0 returns FSE_OK and does nothing. */
 int fsehip_copy_blocks(const uint8_t* d_src, const uint64_t* d_src_offsets, const uint32_t* d_lens, uint32_t n_blocks,
                        uint8_t* d_dst, const uint64_t* d_dst_offsets, fsehip_stream_t stream);
 
@@ -569,7 +588,11 @@ int fsehip_bitstream_read_ops(const uint8_t* d_in, uint64_t n_bytes, uint64_t to
                               const uint8_t* d_ops, uint64_t count, uint32_t* d_vals, uint64_t* d_result,
                               fsehip_stream_t stream);
 
-/* histogram::count per block: d_counts[b*256 + s], d_table_len[b]. */
+/* histogram::count per block of block_size bytes (0 = 65536; a multiple of
+ * 16 when there is more than one block, BAD_ARG otherwise; the last block
+ * may be short): d_counts[b*256 + s], and d_table_len[b] = 1 + the largest
+ * symbol of block b (d_table_len may be NULL).  n_total == 0 counts one
+ * empty block: 256 zeros, table_len 1. */
 int fsehip_histogram_blocks(const uint8_t* d_src, uint64_t n_total, uint32_t block_size, uint32_t* d_counts,
                             uint32_t* d_table_len, fsehip_stream_t stream);
 

@@ -228,8 +228,10 @@ def test_bitstream_peek_advance(torch_cuda):
 
 
 def test_bitstack_device_batched(torch_cuda):
-    """fsehip_bitstack_write / read on 3M device-resident fields against the
-    oracle's writer."""
+    """fsehip_bitstack_write on 3M device-resident fields (no marker) against
+    the oracle's writer, and fsehip_bitstream_read (the forward reader) of the
+    same fields.  The stack reader fsehip_bitstack_read, the per-field ops and
+    the tile / scan-chunk edges are in test_gpu_bits_device.py."""
     import ctypes as C
 
     torch = torch_cuda
