@@ -43,6 +43,8 @@ EXPORTS = (
     "bitstack_writer_write_bits_raw_unmasked", "bitstack_writer_write_bits", "bitstack_writer_write_bits_unmasked",
     "bitstack_writer_finish",
     "fse_compress2_many", "fse_compress_many", "fsehip_compress_streams", "fsehip_stream_out_bytes",
+    "fsehip_frame_bound", "fsehip_frame_read_header", "fsehip_frame_write_header",
+    "fsehip_frame_compress", "fsehip_frame_decompress",
 )
 
 STATUS = {
@@ -50,7 +52,7 @@ STATUS = {
     -5: "BAD_HEADER", -6: "NO_MARKER", -7: "DST_TOO_SMALL", -8: "TABLELOG_RANGE",
     -9: "CURSED", -10: "BAD_TABLE", -11: "BAD_ARG", -12: "HIP", -13: "LENGTH_MISMATCH",
     -14: "UNSUPPORTED", -15: "NO_DEVICE", -16: "BAD_SIDECAR", -17: "ENCODER_INIT",
-    -18: "EOF",
+    -18: "EOF", -19: "BAD_FRAME",
 }
 
 
@@ -72,6 +74,20 @@ class Params(C.Structure):
 class StreamDesc(C.Structure):
     """fsehip_stream_desc: one stream of fsehip_compress_streams."""
     _fields_ = [("src_off", C.c_uint64), ("out_off", C.c_uint64), ("src_len", C.c_uint32), ("out_cap", C.c_uint32)]
+
+
+class FrameInfo(C.Structure):
+    """fsehip_frame_info: a frame's header fields, records_off = 32 + 4 * n_blocks."""
+    _fields_ = [("version", C.c_uint32), ("nstates", C.c_uint32), ("max_table_log", C.c_uint32),
+                ("flags", C.c_uint32), ("block_size", C.c_uint32), ("ckpt_interval", C.c_uint32),
+                ("n_blocks", C.c_uint32), ("reserved", C.c_uint32), ("n_total", C.c_uint64),
+                ("records_off", C.c_uint64)]
+
+
+class FrameParams(C.Structure):
+    """fsehip_frame_params: fsehip_params + chunk_blocks (0 = 4096)."""
+    _fields_ = [("block_size", C.c_uint32), ("table_log", C.c_uint32), ("ckpt_interval", C.c_uint32),
+                ("max_table_log", C.c_uint32), ("nstates", C.c_uint32), ("chunk_blocks", C.c_uint32)]
 
 
 class Histogram(C.Structure):
@@ -175,6 +191,12 @@ def load() -> C.CDLL:
     lib.fsehip_unpack_blocks.argtypes = [P, P, P, u32, P, u64, P]
     lib.fsehip_copy_blocks.argtypes = [P, P, P, u32, P, P, P]
     lib.fsehip_release_workspace.argtypes = [C.c_int, P]
+    lib.fsehip_frame_bound.argtypes = [u64, u32]
+    lib.fsehip_frame_bound.restype = u64
+    lib.fsehip_frame_read_header.argtypes = [P, sz, C.POINTER(FrameInfo)]
+    lib.fsehip_frame_write_header.argtypes = [C.POINTER(FrameInfo), P]
+    lib.fsehip_frame_compress.argtypes = [C.POINTER(FrameParams), P, u64, P, u64, P, P, P]
+    lib.fsehip_frame_decompress.argtypes = [C.POINTER(FrameInfo), u32, P, u64, P, u64, P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     H, NH = C.POINTER(Histogram), C.POINTER(NormHistogram)
     lib.histogram_new.argtypes = [P, sz, H]

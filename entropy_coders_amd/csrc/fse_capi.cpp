@@ -44,7 +44,11 @@ enum {
     SCRATCH_BULK = 4,
     SCRATCH_HDR = 5,  // the lane-parallel header parse's output (optional)
     SCRATCH_SPREAD = 6,  // the L >= 13 encoder's spread symbols when the slots cannot hold them
-    SCRATCH_KINDS = 7
+    // the frame calls, per chunk of blocks (fsehip.h workspace note)
+    SCRATCH_FRAME_SLOTS = 7,  // the chunk's slots
+    SCRATCH_FRAME_META = 8,   // checkpoints, comp_len, status, record type
+    SCRATCH_FRAME_SCAN = 9,   // record offsets + the running frame offset
+    SCRATCH_KINDS = 10
 };
 struct Workspace {
     int dev;
@@ -407,9 +411,11 @@ int fsehip_release_workspace(int device, fsehip_stream_t stream) {
     return rc;
 }
 
-int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_t n_total, uint8_t* d_out,
-                           uint64_t slot_bytes, uint32_t* d_comp_len, uint32_t* d_payload_bits, uint64_t* d_sidecar,
-                           int32_t* d_status, fsehip_stream_t stream) {
+// `held`: the caller's lease on the stream's workspace (the frame calls), or
+// nullptr: the call takes its own when it needs the spread scratch.
+static int compress_blocks_impl(const fsehip_params* p, const uint8_t* d_src, uint64_t n_total, uint8_t* d_out,
+                                uint64_t slot_bytes, uint32_t* d_comp_len, uint32_t* d_payload_bits,
+                                uint64_t* d_sidecar, int32_t* d_status, fsehip_stream_t stream, Lease* held) {
     if (!p || !d_src || !d_out || !d_comp_len || !d_status) return FSE_ERR_BAD_ARG;
     if (n_total == 0) return FSE_ERR_EMPTY;
     const uint32_t bs = p->block_size ? p->block_size : kDefaultBlock;
@@ -450,13 +456,20 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
     // else in a workspace buffer (held until the launch is enqueued)
     std::unique_ptr<Lease> lease;
     if (fsehip::enc_gsym(lmax) && slot_bytes < fsehip::ENC_SPREAD_OFF + (1ull << lmax)) {
-        lease = std::make_unique<Lease>(stream);
-        P.spread = static_cast<uint8_t*>(lease->get(SCRATCH_SPREAD, n_blocks << lmax));
+        if (!held) lease = std::make_unique<Lease>(stream);
+        P.spread = static_cast<uint8_t*>((held ? held : lease.get())->get(SCRATCH_SPREAD, n_blocks << lmax));
         if (!P.spread) return FSE_ERR_HIP;
     }
     hipError_t e = fsehip::launch_encode(P, lmax, static_cast<hipStream_t>(stream));
     if (P.stamps) g_stamps_enc.report("encode", groups, static_cast<hipStream_t>(stream));
     return e == hipSuccess ? FSE_OK : FSE_ERR_HIP;
+}
+
+int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_t n_total, uint8_t* d_out,
+                           uint64_t slot_bytes, uint32_t* d_comp_len, uint32_t* d_payload_bits, uint64_t* d_sidecar,
+                           int32_t* d_status, fsehip_stream_t stream) {
+    return compress_blocks_impl(p, d_src, n_total, d_out, slot_bytes, d_comp_len, d_payload_bits, d_sidecar, d_status,
+                                stream, nullptr);
 }
 
 uint64_t fsehip_stream_out_bytes(uint32_t src_len, uint32_t max_table_log) {
@@ -630,17 +643,24 @@ extern "C++" {
 // Decode tables for all blocks at high occupancy into the stream's
 // workspace, then `run(dt, info, lease)` enqueues the decode on them; both under
 // the workspace lock.
+// (with_dtables_lease: on a lease the caller already holds -- the frame calls)
+template <class Run>
+static int with_dtables_lease(const fsehip_params* p, const uint8_t* d_in, uint64_t slot_bytes,
+                              const uint32_t* d_comp_len, uint64_t n_blocks, fsehip_stream_t stream, Lease& lease,
+                              Run run) {
+    uint32_t* dt = static_cast<uint32_t*>(lease.get(SCRATCH_DT, fsehip_dtable_bytes(p->max_table_log) * n_blocks));
+    int32_t* info = static_cast<int32_t*>(lease.get(SCRATCH_DTINFO, 4ull * n_blocks));
+    if (!dt || !info) return FSE_ERR_HIP;
+    int rc = build_dtables_impl(p, d_in, slot_bytes, d_comp_len, (uint32_t)n_blocks, dt, info, stream, &lease);
+    return rc != FSE_OK ? rc : run(dt, info, lease);
+}
 template <class Run>
 static int with_dtables_n(const fsehip_params* p, const uint8_t* d_in, uint64_t slot_bytes, const uint32_t* d_comp_len,
                           uint64_t n_blocks, fsehip_stream_t stream, Run run) {
     if (n_blocks > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;
     if (!device_ok()) return FSE_ERR_NO_DEVICE;
     Lease lease(stream);
-    uint32_t* dt = static_cast<uint32_t*>(lease.get(SCRATCH_DT, fsehip_dtable_bytes(p->max_table_log) * n_blocks));
-    int32_t* info = static_cast<int32_t*>(lease.get(SCRATCH_DTINFO, 4ull * n_blocks));
-    if (!dt || !info) return FSE_ERR_HIP;
-    int rc = build_dtables_impl(p, d_in, slot_bytes, d_comp_len, (uint32_t)n_blocks, dt, info, stream, &lease);
-    return rc != FSE_OK ? rc : run(dt, info, lease);
+    return with_dtables_lease(p, d_in, slot_bytes, d_comp_len, n_blocks, stream, lease, run);
 }
 template <class Run>
 static int with_dtables(const fsehip_params* p, const uint8_t* d_in, uint64_t slot_bytes, const uint32_t* d_comp_len,
@@ -753,6 +773,160 @@ int fsehip_copy_blocks(const uint8_t* d_src, const uint64_t* d_src_offsets, cons
     hipError_t e = fsehip::launch_copy(d_src, d_src_offsets, d_lens, n_blocks, d_dst, d_dst_offsets,
                                        static_cast<hipStream_t>(stream));
     return e == hipSuccess ? FSE_OK : FSE_ERR_HIP;
+}
+
+// ------------------------------------------------------------------------
+// The frame (fsehip.h section 2b): header in fse_frame.cpp, kernels in
+// fse_frame.hip.  Both calls hold the stream's workspace for all their
+// chunks and lay the chunk scratch out as
+//   META  [cb_cap x spb] u64 checkpoints | comp_len | status | record type
+//   SCAN  [cb_cap] u64 record offsets | u64 running frame offset
+// ------------------------------------------------------------------------
+extern "C++" {
+struct FrameScratch {
+    fsehip::FrameChunk F{};
+    bool ok = false;
+};
+// blocks per chunk: the caller's (0 = 4096), at most n_blocks, and few enough
+// that the chunk's slots stay within 1 GiB
+static uint32_t frame_chunk_blocks(uint32_t chunk_blocks, uint64_t n_blocks, uint64_t slot_bytes) {
+    uint64_t cb = chunk_blocks ? chunk_blocks : 4096u;
+    cb = std::min(cb, std::max<uint64_t>((1ull << 30) / slot_bytes, 1u));
+    return (uint32_t)std::max<uint64_t>(std::min(cb, n_blocks), 1u);
+}
+static FrameScratch frame_scratch(Lease& lease, uint32_t cb_cap, uint64_t slot_bytes, uint32_t spb, bool slots) {
+    FrameScratch S;
+    uint8_t* meta = static_cast<uint8_t*>(lease.get(SCRATCH_FRAME_META, (12ull + 8ull * spb) * cb_cap));
+    uint64_t* scan = static_cast<uint64_t*>(lease.get(SCRATCH_FRAME_SCAN, 8ull * cb_cap + 8u));
+    S.F.slots = slots ? static_cast<uint8_t*>(lease.get(SCRATCH_FRAME_SLOTS, (uint64_t)cb_cap * slot_bytes)) : nullptr;
+    if (!meta || !scan || (slots && !S.F.slots)) return S;
+    S.F.slot_bytes = slot_bytes;
+    S.F.spb = spb;
+    S.F.sidecar = spb ? reinterpret_cast<uint64_t*>(meta) : nullptr;
+    uint8_t* words = meta + 8ull * spb * cb_cap;
+    S.F.comp_len = reinterpret_cast<uint32_t*>(words);
+    S.F.status = reinterpret_cast<int32_t*>(words + 4ull * cb_cap);
+    S.F.kind = reinterpret_cast<uint32_t*>(words + 8ull * cb_cap);
+    S.F.off = scan;
+    S.F.base = scan + cb_cap;
+    S.ok = true;
+    return S;
+}
+}  // extern "C++"
+
+int fsehip_frame_compress(const fsehip_frame_params* p, const uint8_t* d_src, uint64_t n_total, uint8_t* d_frame,
+                          uint64_t frame_cap, uint64_t* d_frame_len, int32_t* d_result, fsehip_stream_t stream) {
+    if (!p || !d_frame || !d_frame_len || !d_result || (n_total && !d_src)) return FSE_ERR_BAD_ARG;
+    const uint32_t bs = p->block_size ? p->block_size : kDefaultBlock;
+    if (bs > kMaxBlock) return FSE_ERR_UNSUPPORTED;
+    const uint64_t n_blocks = (n_total + bs - 1) / bs;
+    if ((n_blocks > 1 && (bs & 15u)) || n_blocks > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;
+    if (p->nstates > 2 || (reinterpret_cast<uintptr_t>(d_src) & 15u)) return FSE_ERR_BAD_ARG;
+    const uint32_t ns = p->nstates == 1 ? 1u : 2u;
+    if (p->ckpt_interval && (p->ckpt_interval < (ns == 1 ? 16u : 8u) || (p->ckpt_interval & (p->ckpt_interval - 1))))
+        return FSE_ERR_BAD_ARG;
+    if (frame_cap < fsehip_frame_bound(n_total, bs)) return FSE_ERR_DST_TOO_SMALL;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    const fsehip_params bp{bs, p->table_log, p->ckpt_interval, p->max_table_log, ns};
+    const uint32_t lmax = kern_lmax(lmax_for(&bp));
+    fsehip_frame_info info{};
+    info.version = 1;
+    info.nstates = ns;
+    info.max_table_log = lmax;
+    info.flags = p->ckpt_interval ? 1u : 0u;
+    info.block_size = bs;
+    info.ckpt_interval = p->ckpt_interval;
+    info.n_blocks = (uint32_t)n_blocks;
+    info.n_total = n_total;
+    uint8_t hb[32];
+    fsehip::FrameHdr hdr;
+    if (fsehip_frame_write_header(&info, hb) != FSE_OK) return FSE_ERR_BAD_ARG;
+    memcpy(hdr.w, hb, sizeof(hb));
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const uint64_t slot_bytes = fsehip_slot_bytes(bs, lmax);
+    const uint32_t spb = fsehip_sidecar_per_block_ns(bs, p->ckpt_interval, ns);
+    const uint32_t cb_cap = frame_chunk_blocks(p->chunk_blocks, n_blocks, slot_bytes);
+    Lease lease(stream);
+    FrameScratch S = frame_scratch(lease, cb_cap, slot_bytes, spb, n_blocks != 0);
+    if (!S.ok) return FSE_ERR_HIP;
+    fsehip::FrameChunk& F = S.F;
+    F.frame = d_frame;
+    F.n_total = n_total;
+    F.block_size = bs;
+    F.ckpt_interval = p->ckpt_interval;
+    F.nstates = ns;
+    F.n_blocks = (uint32_t)n_blocks;
+    F.raw = const_cast<uint8_t*>(d_src);
+    if (n_blocks == 0)  // the header alone
+        return fsehip::launch_frame_plan(F, hdr, true, true, d_frame_len, d_result, hs) == hipSuccess ? FSE_OK
+                                                                                                     : FSE_ERR_HIP;
+    for (uint64_t c0 = 0; c0 < n_blocks; c0 += cb_cap) {
+        F.c0 = (uint32_t)c0;
+        F.cb = (uint32_t)std::min<uint64_t>(cb_cap, n_blocks - c0);
+        const uint64_t chunk_total = std::min<uint64_t>((uint64_t)F.cb * bs, n_total - c0 * bs);
+        // entries the encoder leaves unwritten are stored as zero
+        if (spb && hipMemsetAsync(F.sidecar, 0, 8ull * spb * F.cb, hs) != hipSuccess) return FSE_ERR_HIP;
+        const int rc = compress_blocks_impl(&bp, d_src + c0 * bs, chunk_total, F.slots, slot_bytes, F.comp_len, nullptr,
+                                            F.sidecar, F.status, stream, &lease);
+        if (rc != FSE_OK) return rc;
+        if (fsehip::launch_frame_plan(F, hdr, c0 == 0, c0 + F.cb == n_blocks, d_frame_len, d_result, hs) != hipSuccess ||
+            fsehip::launch_frame_pack(F, hs) != hipSuccess)
+            return FSE_ERR_HIP;
+    }
+    return FSE_OK;
+}
+
+int fsehip_frame_decompress(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                            uint64_t frame_len, uint8_t* d_out, uint64_t out_cap, int32_t* d_block_status,
+                            int32_t* d_result, fsehip_stream_t stream) {
+    if (!info || !d_frame || !d_result || (info->n_total && !d_out)) return FSE_ERR_BAD_ARG;
+    if (info->block_size > kMaxBlock) return FSE_ERR_UNSUPPORTED;
+    uint8_t hb[32];
+    fsehip::FrameHdr hdr;
+    // the rules of fsehip_frame_read_header: nstates, ckpt_interval, n_blocks = ceil(n_total / block_size), ...
+    if (fsehip_frame_write_header(info, hb) != FSE_OK || (reinterpret_cast<uintptr_t>(d_out) & 15u))
+        return FSE_ERR_BAD_ARG;
+    if (out_cap < info->n_total) return FSE_ERR_DST_TOO_SMALL;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    memcpy(hdr.w, hb, sizeof(hb));
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const uint32_t bs = info->block_size, ns = info->nstates, ckpt = info->ckpt_interval;
+    const uint64_t n_blocks = info->n_blocks;
+    const fsehip_params bp{bs, 0, ckpt, info->max_table_log, ns};
+    const uint64_t slot_bytes = fsehip_slot_bytes(bs, info->max_table_log);
+    const uint32_t spb = fsehip_sidecar_per_block_ns(bs, ckpt, ns);
+    const uint32_t cb_cap = frame_chunk_blocks(chunk_blocks, n_blocks, slot_bytes);
+    Lease lease(stream);
+    FrameScratch S = frame_scratch(lease, cb_cap, slot_bytes, spb, n_blocks != 0);
+    if (!S.ok) return FSE_ERR_HIP;
+    fsehip::FrameChunk& F = S.F;
+    F.frame = const_cast<uint8_t*>(d_frame);
+    F.frame_len = frame_len;
+    F.n_total = info->n_total;
+    F.block_size = bs;
+    F.ckpt_interval = ckpt;
+    F.nstates = ns;
+    F.n_blocks = (uint32_t)n_blocks;
+    F.raw = d_out;
+    if (fsehip::launch_frame_check(F, hdr, d_result, hs) != hipSuccess) return FSE_ERR_HIP;
+    for (uint64_t c0 = 0; c0 < n_blocks; c0 += cb_cap) {
+        F.c0 = (uint32_t)c0;
+        F.cb = (uint32_t)std::min<uint64_t>(cb_cap, n_blocks - c0);
+        const uint64_t chunk_total = std::min<uint64_t>((uint64_t)F.cb * bs, info->n_total - c0 * bs);
+        if (fsehip::launch_frame_scan(F, hs) != hipSuccess || fsehip::launch_frame_unpack(F, hs) != hipSuccess)
+            return FSE_ERR_HIP;
+        // non-FSE blocks have comp_len 0: their table build fails and no decode kernel touches their output
+        uint8_t* out = d_out + c0 * bs;
+        const int rc = with_dtables_lease(&bp, F.slots, slot_bytes, F.comp_len, F.cb, stream, lease,
+                                          [&](const uint32_t* dt, const int32_t* dti, Lease& l) {
+                                              return decompress_impl(&bp, F.slots, slot_bytes, F.comp_len, F.sidecar, out,
+                                                                     chunk_total, nullptr, F.status, nullptr, 0, stream,
+                                                                     dt, dti, &l);
+                                          });
+        if (rc != FSE_OK) return rc;
+        if (fsehip::launch_frame_merge(F, d_block_status, d_result, hs) != hipSuccess) return FSE_ERR_HIP;
+    }
+    return FSE_OK;
 }
 
 int fsehip_generate(int kind, double prob, uint64_t seed, uint32_t block_size, uint8_t* d_out, uint64_t n_total,

@@ -195,4 +195,43 @@ hipError_t launch_copy(const uint8_t* src, const uint64_t* src_off, const uint32
 hipError_t launch_stream_offsets(const uint32_t* lens, uint32_t n, uint64_t* offsets, uint64_t* total,
                                  hipStream_t hs);
 
+// The frame (fsehip.h section 2b; fse_frame.hip).  One call works on the
+// blocks [c0, c0 + cb) of the frame -- a chunk -- with chunk-local scratch
+// arrays (index i = b - c0): the encoder's / decoder's slots, comp_len,
+// status and sidecar (stride spb entries), the record type `kind` and the
+// record's absolute frame offset `off`.  *base is the running frame offset
+// between chunks (decode: 0 = the frame failed its check, nothing is copied).
+struct FrameHdr {
+    uint32_t w[8];  // the 32 header bytes as little-endian words
+};
+struct FrameChunk {
+    uint8_t* frame;  // any alignment
+    uint64_t frame_len;  // decode only
+    uint64_t n_total;
+    uint32_t block_size, ckpt_interval, nstates, n_blocks;
+    uint32_t c0, cb;
+    uint8_t* slots;
+    uint64_t slot_bytes;
+    uint32_t* comp_len;
+    int32_t* status;
+    uint64_t* sidecar;  // nullptr without checkpoints
+    uint32_t spb;
+    uint32_t* kind;
+    uint64_t* off;
+    uint64_t* base;
+    uint8_t* raw;  // encode: the source; decode: the output
+};
+// encode: rule + directory + offsets (first: start a frame; last: write the
+// header, *frame_len and result[0]); then the records
+hipError_t launch_frame_plan(const FrameChunk& F, const FrameHdr& hdr, bool first, bool last, uint64_t* frame_len,
+                             int32_t* result, hipStream_t hs);
+hipError_t launch_frame_pack(const FrameChunk& F, hipStream_t hs);
+// decode: whole-frame check (header == hdr, directory ends at frame_len;
+// writes *base and result), then per chunk validate + offsets, scatter /
+// copy / fill, and the status merge
+hipError_t launch_frame_check(const FrameChunk& F, const FrameHdr& hdr, int32_t* result, hipStream_t hs);
+hipError_t launch_frame_scan(const FrameChunk& F, hipStream_t hs);
+hipError_t launch_frame_unpack(const FrameChunk& F, hipStream_t hs);
+hipError_t launch_frame_merge(const FrameChunk& F, int32_t* block_status, int32_t* result, hipStream_t hs);
+
 }  // namespace fsehip

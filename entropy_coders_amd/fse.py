@@ -11,8 +11,8 @@ import threading
 
 import numpy as np
 
-from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, EncodeTable, FseError,
-                   Histogram, NormHistogram, Params, check, load)
+from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, EncodeTable, FrameInfo,
+                   FrameParams, FseError, Histogram, NormHistogram, Params, check, load)
 
 
 def _buf(data) -> np.ndarray:
@@ -657,6 +657,71 @@ class BlockCodec:
                                        n_total, self._stream()), "fsehip_generate")
         return out
 
+    # ------------------------------------------------------------ the frame
+    # fsehip.h section 2b: one self-describing buffer for any input (RAW /
+    # RLE fallback per block), this library's own container.
+    def frame_bound(self, n: int) -> int:
+        """`fsehip_frame_bound`: a capacity no frame of n bytes exceeds."""
+        return int(self.lib.fsehip_frame_bound(n, self.block_size))
+
+    def compress_frame_into(self, src, frame, frame_len, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_frame_compress`, no synchronisation: `frame` a uint8 device
+        tensor of >= frame_bound(src.numel()) bytes (any alignment),
+        `frame_len` one int64, `result` two int32 (frame status, blocks not
+        stored as FSE)."""
+        p = FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
+                        chunk_blocks)
+        check(self.lib.fsehip_frame_compress(
+            C.byref(p), C.c_void_p(src.data_ptr()), src.numel(), C.c_void_p(frame.data_ptr()), frame.numel(),
+            C.c_void_p(frame_len.data_ptr()), C.c_void_p(result.data_ptr()), self._stream()), "fsehip_frame_compress")
+
+    def compress_frame(self, src, chunk_blocks: int = 0):
+        """Compress any uint8 device tensor (empty included) into one frame: a
+        uint8 device tensor of the frame's exact length.  One
+        synchronisation, to read the length."""
+        t = self.torch
+        frame = t.empty(self.frame_bound(src.numel()), dtype=t.uint8, device=self.device)
+        frame_len = t.zeros(1, dtype=t.int64, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.compress_frame_into(src, frame, frame_len, result, chunk_blocks)
+        return frame[: int(frame_len.item())]
+
+    @staticmethod
+    def frame_info(frame) -> FrameInfo:
+        """`fsehip_frame_read_header` of a frame given as bytes, a numpy array
+        or a tensor (its first 32 bytes come to the host); raises FseError
+        (BAD_FRAME) for anything that is not a frame header."""
+        if hasattr(frame, "data_ptr"):  # a torch tensor
+            head = frame[:32].cpu().numpy().tobytes()
+        else:
+            head = bytes(memoryview(frame)[:32])
+        a = np.frombuffer(head, dtype=np.uint8)
+        info = FrameInfo()
+        check(load().fsehip_frame_read_header(_p(a), len(a), C.byref(info)), "fsehip_frame_read_header")
+        return info
+
+    def decompress_frame_into(self, frame, info: FrameInfo, out, block_status, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_frame_decompress`, no synchronisation: `out` >= info.n_total
+        bytes (16-byte aligned), `block_status` info.n_blocks int32 or None,
+        `result` two int32 (frame status, failed blocks)."""
+        check(self.lib.fsehip_frame_decompress(
+            C.byref(info), chunk_blocks, C.c_void_p(frame.data_ptr()), frame.numel(), C.c_void_p(out.data_ptr()),
+            out.numel(), C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_frame_decompress")
+
+    def decompress_frame(self, frame, chunk_blocks: int = 0):
+        """Decode a frame (a uint8 device tensor) from its bytes alone: the
+        codec's own parameters play no part.  Returns (out, block_status);
+        raises FseError for a frame-level error (BAD_FRAME)."""
+        t = self.torch
+        info = self.frame_info(frame)
+        out = t.empty(info.n_total, dtype=t.uint8, device=self.device)
+        status = t.zeros(info.n_blocks, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_frame_into(frame, info, out, status, result, chunk_blocks)
+        check(int(result[0].item()), "frame")
+        return out, status
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -664,10 +729,38 @@ class BlockCodec:
         return cb["out"][s: s + ln].cpu().numpy().tobytes()
 
 
+def frame_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
+                   device=None) -> bytes:
+    """Compress any host buffer (bytes, numpy; empty included) into one frame
+    (fsehip.h section 2b) on the GPU; copies through torch."""
+    import torch
+
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    src = torch.from_numpy(_buf(data).copy()).to(codec.device)
+    return codec.compress_frame(src).cpu().numpy().tobytes()
+
+
+def frame_decompress(data, device=None) -> bytes:
+    """Decode a frame held in host memory; raises FseError on a frame-level
+    error (BAD_FRAME) or with the first failed block's status."""
+    import torch
+
+    codec = BlockCodec(device=device)
+    BlockCodec.frame_info(_buf(data))  # not a frame: BAD_FRAME before any device work
+    frame = torch.from_numpy(_buf(data).copy()).to(codec.device)
+    out, status = codec.decompress_frame(frame)
+    st = status.cpu().numpy()
+    if st.any():
+        b = int(np.flatnonzero(st)[0])
+        raise FseError(int(st[b]), f"frame block {b}")
+    return out.cpu().numpy().tobytes()
+
+
 __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStackWriter", "BitStreamReader", "BlockCodec", "DecodeTable", "EncodeTable", "FseError",
            "Histogram", "NormHistogram", "bitstack_read", "bitstack_write", "bitstream_read", "compress", "compress2",
            "compress2_log", "compress2_many", "compress_nh", "compress_streams", "decode_table_new", "decompress", "decompress2", "decompress2_many",
            "decompress_streams",
-           "encode_table_new",
+           "encode_table_new", "frame_compress", "frame_decompress",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal"]

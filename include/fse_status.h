@@ -64,5 +64,10 @@
  * cursor readers of fsehip.h section 1c; the reference's callers treat it as
  * end of stream.                                                            */
 #define FSE_ERR_EOF (-18)
+/* A frame (fsehip.h section 2b, this library's own container) is not one:
+ * bad magic, version or header field, a nonzero reserved word, fewer than 32
+ * bytes, n_blocks != ceil(n_total / block_size), a directory that does not
+ * add up to the frame's length, or (per block) an invalid directory entry.  */
+#define FSE_ERR_BAD_FRAME (-19)
 
 #endif

@@ -406,7 +406,17 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
  *   header parse   520 bytes per block (the headers parsed one per lane
  *                  before the table build: batches of >= 256 blocks at
  *                  max_table_log <= 12, fsehip_build_dtables included;
- *                  without it the tables kernel parses on its own).
+ *                  without it the tables kernel parses on its own);
+ *   frame chunk    (fsehip_frame_compress / fsehip_frame_decompress, per chunk
+ *                  of chunk_blocks blocks, whatever n_total is)
+ *                  chunk_blocks * slot_bytes          the chunk's slots,
+ *                  (12 + 8 * spb) * chunk_blocks      comp_len, status, record
+ *                                                     type and checkpoints
+ *                                                     (spb entries per block),
+ *                  8 * chunk_blocks + 8               record offsets and the
+ *                                                     running frame offset,
+ *                  plus the encode-spread / decode-table / deferred-symbol
+ *                  entries above for a batch of chunk_blocks blocks.
  * Growing a buffer synchronises the stream before freeing the old one.
  * First table build on a device (any encode or decode call): the library
  * first runs a ~1 ms synchronous self-check on the null stream (the lane
@@ -566,6 +576,126 @@ int fsehip_unpack_blocks(const uint8_t* d_stream, const uint64_t* d_offsets, con
  * n_blocks == 0 returns FSE_OK and does nothing. */
 int fsehip_copy_blocks(const uint8_t* d_src, const uint64_t* d_src_offsets, const uint32_t* d_lens, uint32_t n_blocks,
                        uint8_t* d_dst, const uint64_t* d_dst_offsets, fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * (2b) The frame: one self-describing buffer for any input
+ *
+ * This library's own container around the crate-exact blocks (it is not a
+ * crate format).  compress(anything) gives one buffer that decodes from its
+ * bytes alone, never expands beyond fsehip_frame_bound, and round-trips the
+ * inputs the block codec refuses (all zeros, a 1-byte tail, the crate's
+ * panics, an empty input).  Version 1; integers little-endian, no padding,
+ * a frame may start at any byte address:
+ *
+ *   header, 32 bytes
+ *      0  u8[4] magic "FSEF"
+ *      4  u8    version = 1
+ *      5  u8    nstates (1 or 2)
+ *      6  u8    max_table_log  kernel class the blocks were encoded under (11..15)
+ *      7  u8    flags          bit 0: records carry decode checkpoints; others 0
+ *      8  u32   block_size     1..2^28; a multiple of 16 when n_blocks > 1
+ *     12  u32   ckpt_interval  0 when flags bit 0 is clear; else a power of two,
+ *                              >= 8 (2-state) / >= 16 (1-state)
+ *     16  u64   n_total        raw bytes
+ *     24  u32   n_blocks       = ceil(n_total / block_size); 0 for an empty input
+ *     28  u32   reserved = 0
+ *   directory, n_blocks x u32: type << 30 | stored_len
+ *      type 0 RAW  stored_len = raw_len_b  the block's bytes as they are
+ *      type 1 RLE  stored_len = 1          one byte, repeated raw_len_b times
+ *      type 2 FSE  stored_len = comp_len   the crate-exact header||payload
+ *      type 3 invalid
+ *   records, back to back in block order from byte 32 + 4 * n_blocks
+ *      RAW / RLE: stored_len bytes
+ *      FSE: [spb_b x u64 checkpoints, when flags bit 0] then stored_len bytes
+ *
+ * raw_len_b = min(block_size, n_total - b * block_size); spb_b =
+ * fsehip_sidecar_per_block_ns(raw_len_b, ckpt_interval, nstates); the
+ * checkpoints are the entries fsehip_compress_blocks writes for the block
+ * into a zero-filled sidecar (entries it leaves unwritten are zero).  The
+ * frame ends with its last record; a decoder rejects any other length.
+ *
+ * Encoder rule (frames are deterministic): with rec = comp_len + 8 * spb_b
+ * (comp_len alone without checkpoints), block b is RLE of byte 0 iff its
+ * encode status is ALL_ZERO_SYMBOL0, FSE iff the status is FSE_OK and
+ * rec < raw_len_b, RAW otherwise (every other status, every block that would
+ * not shrink).  Hence frame_len <= 32 + 4 * n_blocks + n_total.  A decoder
+ * accepts RLE of any byte.
+ * ------------------------------------------------------------------------ */
+
+/* The header's fields, plus records_off = 32 + 4 * n_blocks. */
+typedef struct {
+    uint32_t version, nstates, max_table_log, flags;
+    uint32_t block_size, ckpt_interval, n_blocks, reserved;
+    uint64_t n_total, records_off;
+} fsehip_frame_info;
+
+/* 32 + 4 * ceil(n_total / block_size) + n_total (block_size 0 = 65536): a
+ * capacity no frame of n_total bytes exceeds. */
+uint64_t fsehip_frame_bound(uint64_t n_total, uint32_t block_size);
+/* Parse and validate the first 32 bytes of a frame (host pointer; len = bytes
+ * available, only the first 32 are read).  FSE_ERR_BAD_FRAME for len < 32,
+ * bad magic / version / field, a nonzero reserved word or flag bit, or
+ * n_blocks != ceil(n_total / block_size). */
+int fsehip_frame_read_header(const uint8_t* hdr, size_t len, fsehip_frame_info* out);
+/* The 32 header bytes of `info` (records_off is not stored); BAD_ARG when
+ * the fields would not pass fsehip_frame_read_header. */
+int fsehip_frame_write_header(const fsehip_frame_info* info, uint8_t hdr[32]);
+
+typedef struct {
+    uint32_t block_size, table_log, ckpt_interval, max_table_log, nstates; /* as fsehip_params */
+    uint32_t chunk_blocks; /* blocks encoded per pass; 0 = 4096 */
+} fsehip_frame_params;
+
+/* Compress n_total bytes (0 is valid: a 32-byte frame) into one frame at
+ * d_frame (any byte alignment; frame_cap >= fsehip_frame_bound, else
+ * DST_TOO_SMALL).  *d_frame_len = the frame's length, d_result[0] = frame
+ * status (FSE_OK), d_result[1] = blocks not stored as FSE.  Only the first
+ * *d_frame_len bytes of d_frame are written.  d_src 16-byte aligned; RAW
+ * blocks are copied from it in 16-byte or aligned 4-byte reads, so up to
+ * roundup(n_total, 4) bytes of it are read.
+ *
+ * Works in chunks of chunk_blocks blocks (fewer when chunk_blocks slots would
+ * exceed 1 GiB), so the workspace is bounded whatever n_total is (the frame
+ * entries of the workspace note at fsehip_decompress_blocks); where the split
+ * falls does not show in the frame.  Per chunk: the batch encoder into slot
+ * scratch, a plan kernel (encoder rule, directory, record offsets), a pack
+ * kernel (one workgroup per block).
+ *
+ * Asynchronous on `stream`, no host synchronisation except when the
+ * workspace grows.  Before any device use: BAD_ARG (null pointer, nstates >
+ * 2, a bad ckpt_interval, block_size not a multiple of 16 with more than one
+ * block, d_src not 16-byte aligned), UNSUPPORTED (block_size > 2^28),
+ * DST_TOO_SMALL, NO_DEVICE. */
+int fsehip_frame_compress(const fsehip_frame_params* p, const uint8_t* d_src, uint64_t n_total, uint8_t* d_frame,
+                          uint64_t frame_cap, uint64_t* d_frame_len, int32_t* d_result, fsehip_stream_t stream);
+
+/* Decompress the frame of frame_len bytes at d_frame (any alignment) whose
+ * header fsehip_frame_read_header parsed into `info` (the caller copies the
+ * 32 bytes to the host).  d_out: info->n_total bytes (out_cap >= n_total,
+ * else DST_TOO_SMALL), 16-byte aligned.  d_block_status (n_blocks entries,
+ * may be NULL): FSE_OK, the block decoder's status for an FSE block, or
+ * BAD_FRAME for a bad directory entry (type 3, a RAW length other than
+ * raw_len_b, an RLE length other than 1, an FSE length of 0 or above
+ * fsehip_slot_bytes(block_size, max_table_log)); such a block alone is
+ * skipped.  d_result[0] = frame status, d_result[1] = failed blocks.
+ *
+ * Before anything is copied a kernel checks that the header on the device
+ * equals `info` and that the directory's record lengths (stored_len, plus
+ * the checkpoints of a type-2 entry) end exactly at frame_len; so every
+ * offset a copy uses lies inside the frame.  A frame that fails this gets
+ * d_result[0] = BAD_FRAME, every block status BAD_FRAME, and no byte of
+ * d_out is touched.  Reads of d_frame: its bytes, in 16-byte or aligned
+ * 4-byte accesses that hold at least one byte of the frame.
+ *
+ * Chunked as the compress side (chunk_blocks 0 = 4096): records are
+ * scattered into slot scratch (RAW copied, RLE filled straight into d_out),
+ * then the table build and decode of fsehip_decompress_blocks run on the
+ * chunk -- segment-parallel with checkpoints, serial without.  Asynchronous;
+ * call-level errors as fsehip_frame_compress (BAD_ARG also for an `info`
+ * that fsehip_frame_read_header would reject or a misaligned d_out). */
+int fsehip_frame_decompress(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                            uint64_t frame_len, uint8_t* d_out, uint64_t out_cap, int32_t* d_block_status,
+                            int32_t* d_result, fsehip_stream_t stream);
 
 /* The bitstream as device passes over `count` fields (a prefix scan of the
  * widths places every field; HBM-bound).
