@@ -142,7 +142,7 @@ int release_workspaces(int device, void* stream, bool any_stream) {
 }
 
 // Tuning / ablation / diagnostics knobs (FSEHIP_ENC_LANES, FSEHIP_DEBUG,
-// FSEHIP_STAMPS, FSEHIP_SERIAL_*, FSEHIP_*_XLDS; see fse_kernels.h) exist
+// FSEHIP_STAMPS, FSEHIP_SERIAL_*, FSEHIP_*_XLDS, FSEHIP_ENC_WGS; see fse_kernels.h) exist
 // only in the diagnostics build libfsehip_diag.so (make diag, -DFSEHIP_DIAG):
 // several of them change the output on purpose (ablations).  The product
 // libfsehip.so reads no environment variable -- every call's result depends
@@ -448,6 +448,7 @@ static int compress_blocks_impl(const fsehip_params* p, const uint8_t* d_src, ui
     P.lanes = (ns == 2 && env_u32("FSEHIP_ENC_LANES", 64) == 32) ? 32 : 64;
     P.debug = env_u32("FSEHIP_DEBUG", 0);
     P.xlds = env_u32("FSEHIP_ENC_XLDS", 0);  // diagnostics: occupancy probe
+    P.enc_wgs = env_u32("FSEHIP_ENC_WGS", 0);  // diagnostics: workgroups per CU by whole LDS granules
     P.rank_inject = env_u32("FSEHIP_RANK_INJECT", 0);  // diagnostics: fault injection into the atomic ranks
     const size_t groups = (n_blocks * P.lanes + 63) / 64;
     P.stamps = g_stamps_enc.get(groups);
@@ -503,6 +504,7 @@ int fsehip_compress_streams(uint32_t nstates, uint32_t table_log, uint32_t max_t
     P.payload_bits = d_payload_bits;
     P.status = d_status;
     P.lanes = 64;
+    P.enc_wgs = env_u32("FSEHIP_ENC_WGS", 0);  // diagnostics: workgroups per CU by whole LDS granules
     P.desc = d_desc;
     // L >= 13: the spread's symbols always in the workspace (a region may be
     // far smaller than 512 + 2^L bytes); the lease is held until the launch

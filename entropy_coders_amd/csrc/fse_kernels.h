@@ -30,6 +30,8 @@ struct EncParams {
     uint32_t xlds;            // diagnostics: extra dynamic LDS bytes per workgroup (occupancy probe)
     uint32_t peer_ranks;      // set by launch_encode: 1 = peer-mask ranks (forced by rank_mode)
     uint32_t rank_inject;     // diagnostics build only: fault injection into the atomic ranks (FSEHIP_RANK_INJECT)
+    uint32_t enc_wgs;         // diagnostics build only: resident workgroups per CU of the L <= 11 kernels, by
+                              // whole LDS granules (FSEHIP_ENC_WGS: 10, 11 or 12; 0 = the launcher's default)
     // kernels at L >= 13 (enc_gsym): the spread's 2^LMAX-byte symbol array of
     // block b at spread + b * 2^LMAX, or (nullptr) in the block's own output
     // slot after its header words, when slot_bytes >= HDR_MAX + 2^LMAX

@@ -592,12 +592,20 @@ struct EncSmem {
     // (2^L bytes) in st[b], the rank loop's peer masks (512 B) in tt[b]
     static constexpr uint32_t HS = BPW == 1 ? HSUB : 8u;
     static_assert(BPW == 1 || 2u * SIZE >= hist_words<8>() * 4u, "sub-histograms fit the stateTable");
+    // One block per wave at L <= 11: the 16 copies (8,320 B) are longer than
+    // st + tt (6,144 B).  They are live only inside wave_histogram, the
+    // first thing a block does, so there they are a view from the struct's
+    // first byte that runs on over the front of `ph` (p1.u and the start of
+    // p1.norm, first written after the histogram is folded into p1.cnt)
+    // instead of a member that sizes the struct: 12,592 B, not 14,768 B.
+    static constexpr bool HIST_OVERLAY = BPW == 1 && LMAX <= 11;
+    static constexpr uint32_t HIST_BYTES = hist_words<HS>() * 4u;
     union {
         struct {
             __attribute__((aligned(16))) uint16_t st[BPW][SIZE];
             uint2 tt[BPW][256];
         };
-        __attribute__((aligned(16))) uint32_t hist[BPW == 1 ? hist_words<HS>() : 4];
+        __attribute__((aligned(16))) uint32_t hist[BPW == 1 && !HIST_OVERLAY ? hist_words<HS>() : 4];
     };
     // phase-1 scratch (statistics, header, spread) and phase-2 scratch
     // (trajectories, end states, merge list) share the same LDS
@@ -634,7 +642,28 @@ struct EncSmem {
         if constexpr (TAIL_IN_P2) return ph.p2.u.tail[0];
         else return tail_out[0];
     }
+    // the sub-histograms of a wave's only block (BPW == 1)
+    __device__ __forceinline__ uint32_t* hist_view() {
+        if constexpr (HIST_OVERLAY) return reinterpret_cast<uint32_t*>(this);
+        else return hist;
+    }
 };
+// What the overlaid sub-histogram view relies on (encode_body, phase 1): it
+// starts at the struct's first byte; past st / tt it covers only p1.u (hdrw /
+// sym_at) and the front of p1.norm, which wave_normalize, wave_header_write
+// and the spread first write after wave_histogram has returned; it ends below
+// p1.cumul and p1.cnt (the histogram's own output, which survives the
+// re-zeroing between the segments of a block longer than HIST_SEG) and far
+// below the tail.
+template <int LMAX, int T>
+constexpr bool enc_overlay_ok() {
+    using S = EncSmem<LMAX, T>;
+    if (!S::HIST_OVERLAY) return sizeof(S::hist) >= (S::BPW == 1 ? S::HIST_BYTES : 16u);
+    return offsetof(S, st) == 0 && S::HIST_BYTES > offsetof(S, ph) &&
+           offsetof(S, ph) + offsetof(decltype(S::ph), p1.cumul) >= S::HIST_BYTES &&
+           offsetof(S, ph) + offsetof(decltype(S::ph), p1.cnt) >= S::HIST_BYTES &&
+           offsetof(S, tail_out) >= S::HIST_BYTES && !S::TAIL_IN_P2;
+}
 
 // Where a block's bytes come from and go to.  Blocks: equal pieces of one
 // buffer into equal slots (worst-case sized).  Streams: a descriptor per
@@ -674,6 +703,7 @@ __device__ __forceinline__ void encode_body(const EncParams& P, EncSmem<LMAX, T>
     static_assert(!EncSmem<LMAX, T>::TAIL_IN_P2 ||
                       64u * track_slots<LMAX>() * 12u + 4u * (T + 1u) >= sizeof(sm.ph.p1),
                   "tail overlaps phase-1 scratch");
+    static_assert(enc_overlay_ok<LMAX, T>(), "sub-histogram view over live phase-1 bytes");
 #define ENC_WGID ((uint64_t)blockIdx.x)
 #define ENC_SYNC() __syncthreads()
     const uint32_t lane = lane_id();
@@ -692,7 +722,7 @@ __device__ __forceinline__ void encode_body(const EncParams& P, EncSmem<LMAX, T>
         uint32_t* counts = sm.ph.p1.cnt;  // the spread reuses cnt[] after normalize
         using Sm = EncSmem<LMAX, T>;
         const uint32_t tl = wave_histogram<Sm::HS>(
-            blk, n, BPW == 1 ? sm.hist : reinterpret_cast<uint32_t*>(sm.st[b]), counts);
+            blk, n, BPW == 1 ? sm.hist_view() : reinterpret_cast<uint32_t*>(sm.st[b]), counts);
         FSE_STAMP(P, 1);
         if (FSE_ABLATE(P, 8u)) {  // ablation: histogram only
             if (lane == 0) P.status[gb] = (int32_t)tl;
@@ -1209,7 +1239,30 @@ __global__ __launch_bounds__(256) void generate_kernel(GenParams G) {
 // ------------------------------------------------------------------------
 // launch wrappers
 // ------------------------------------------------------------------------
-constexpr uint32_t ENC_WGS = 11u;  // resident encode workgroups per CU at L <= 11 (LDS-padded)
+// LDS is allocated to a workgroup in granules of 1,280 B, 128 to a CU
+// (measured, tools/micro/occ_probe.hip: one-wave workgroups are 12 per CU up
+// to 12,800 B, 11 up to 14,080 B, 10 up to 15,360 B; the occupancy API
+// models 512 B and answers one too many between the steps).
+constexpr uint32_t LDS_GRANULE = 1280u, LDS_CU = 160u << 10;
+// Resident encode workgroups per CU at L <= 11; 0 = as many as fit, which is
+// 12 for the 12,592 B kernels (no pad).  A lower count is had by padding the
+// workgroup's LDS to the most whole granules that still fit that many times.
+constexpr uint32_t ENC_WGS = 0u;
+template <auto KERN>
+uint32_t enc_static_lds() {
+    static const uint32_t lds = [] {
+        hipFuncAttributes fa{};
+        return hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(KERN)) == hipSuccess ? (uint32_t)fa.sharedSizeBytes
+                                                                                             : 0u;
+    }();
+    return lds;
+}
+template <auto KERN>
+uint32_t enc_pad(uint32_t wgs) {
+    if (wgs == 0u) return 0u;
+    const uint32_t lds = enc_static_lds<KERN>(), per = LDS_CU / wgs / LDS_GRANULE * LDS_GRANULE;
+    return lds && lds < per ? per - lds : 0u;
+}
 hipError_t launch_encode(const EncParams& P0, uint32_t lmax, hipStream_t stream) {
     EncParams P = P0;
     P.peer_ranks = atomic_ranks_on() ? 0u : 1u;
@@ -1219,28 +1272,21 @@ hipError_t launch_encode(const EncParams& P0, uint32_t lmax, hipStream_t stream)
     const uint32_t bpw = 64u / T;
     const dim3 g((P.n_blocks + bpw - 1u) / bpw), b(64);
     auto go = [&](auto kern, uint32_t pad = 0) { hipLaunchKernelGGL(kern, g, b, P.xlds ? P.xlds : pad, stream, P); };
+    // L <= 11, one block per wave (diagnostics: enc_wgs picks 10, 11 or 12)
+    const uint32_t wgs = P.enc_wgs ? P.enc_wgs : ENC_WGS;
     if (P.desc) {
         // streams form: one stream per wave, by table-log class as below
         if (enc_gsym(lmax) && !P.spread) return hipErrorInvalidValue;
         const dim3 gs(P.n_blocks);
         auto gos = [&](auto kern, uint32_t pad = 0) { hipLaunchKernelGGL(kern, gs, b, pad, stream, P); };
         if (P.nstates == 1) {
-            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 1>);
+            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 1>, enc_pad<encode_streams_kernel<11, 64, 1>>(wgs));
             else if (lmax <= 12) gos(encode_streams_kernel<12, 64, 1>);
             else if (lmax <= 13) gos(encode_streams_kernel<13, 64, 1>);
             else if (lmax <= 14) gos(encode_streams_kernel<14, 64, 1>);
             else gos(encode_streams_kernel<15, 64, 1>);
         } else {
-            // the same 11 workgroups per CU as the block kernel (pad11 below)
-            static const uint32_t pad11s = [] {
-                hipFuncAttributes fa{};
-                if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(encode_streams_kernel<11, 64, 2>)) !=
-                    hipSuccess)
-                    return 0u;
-                const size_t per = (160u << 10) / ENC_WGS - 64u;
-                return fa.sharedSizeBytes < per ? (uint32_t)(per - fa.sharedSizeBytes) : 0u;
-            }();
-            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 2>, pad11s);
+            if (lmax <= 11) gos(encode_streams_kernel<11, 64, 2>, enc_pad<encode_streams_kernel<11, 64, 2>>(wgs));
             else if (lmax <= 12) gos(encode_streams_kernel<12, 64, 2>);
             else if (lmax <= 13) gos(encode_streams_kernel<13, 64, 2>);
             else if (lmax <= 14) gos(encode_streams_kernel<14, 64, 2>);
@@ -1249,25 +1295,17 @@ hipError_t launch_encode(const EncParams& P0, uint32_t lmax, hipStream_t stream)
         return hipGetLastError();
     }
     if (P.nstates == 1) {  // fse_compress (lib.rs:112-143)
-        if (lmax <= 11) go(encode_blocks_kernel<11, 64, 1>);
+        if (lmax <= 11) go(encode_blocks_kernel<11, 64, 1>, enc_pad<encode_blocks_kernel<11, 64, 1>>(wgs));
         else if (lmax <= 12) go(encode_blocks_kernel<12, 64, 1>);
         else if (lmax <= 13) go(encode_blocks_kernel<13, 64, 1>);
         else if (lmax <= 14) go(encode_blocks_kernel<14, 64, 1>);
         else go(encode_blocks_kernel<15, 64, 1>);
     } else if (T == 64) {
-        // 11 workgroups per CU rather than the 12 its 12.6 KB allowed in
-        // round 3: same time on C2, 5% less on near-uniform data
-        // (tools/occ_enc.py, one process: 12 -> 2.00 ms, 11 -> 1.90, 10 ->
-        // 1.88; C2 1.58 / 1.57 / 1.61), where the twelfth workgroup only adds
-        // contention.  (At 14.6 KB, round 5, 11 is also the most that fit.)
-        static const uint32_t pad11 = [] {
-            hipFuncAttributes fa{};
-            if (hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(encode_blocks_kernel<11, 64, 2>)) != hipSuccess)
-                return 0u;
-            const size_t per = (160u << 10) / ENC_WGS - 64u;  // LDS per workgroup for 11, less allocation slack
-            return fa.sharedSizeBytes < per ? (uint32_t)(per - fa.sharedSizeBytes) : 0u;
-        }();
-        if (lmax <= 11) go(encode_blocks_kernel<11, 64, 2>, pad11);
+        // (Rounds 3-6 padded this kernel "to 11 per CU" on a 512 B granule
+        // model: its 14,830 B were 12 granules and 10 per CU, and the 10 / 11 /
+        // 12 comparison of round 3 compared other counts than it named.  The
+        // comparison by whole granules: profiles/enc_occ/.)
+        if (lmax <= 11) go(encode_blocks_kernel<11, 64, 2>, enc_pad<encode_blocks_kernel<11, 64, 2>>(wgs));
         else if (lmax <= 12) go(encode_blocks_kernel<12, 64, 2>);
         else if (lmax <= 13) go(encode_blocks_kernel<13, 64, 2>);
         else if (lmax <= 14) go(encode_blocks_kernel<14, 64, 2>);

@@ -17,8 +17,7 @@ import torch  # noqa: E402
 from entropy_coders_amd import BlockCodec  # noqa: E402
 from tools.ablate import timeit  # noqa: E402
 
-LDS_CU = 160 * 1024
-BASE = int(os.environ.get("OCC_BASE_LDS", 14656))
+from tools.occ_enc import pad_for, resident, static_lds  # noqa: E402  (whole 1,280 B granules)
 
 
 def main():
@@ -28,11 +27,12 @@ def main():
     codec = BlockCodec(table_log=tlog)
     src = codec.generate(kind, prob, 0x5EED0002, n)
     cb = codec.alloc(n)
-    wgs = [int(x) for x in os.environ.get("OCC_WGS", "11,8,6,4").split(",")]
+    wgs = [int(x) for x in os.environ.get("OCC_WGS", "12,10,8,6,4").split(",")]
     abl = [(8, "hist"), (1, "tables"), (18, "count"), (2, "repair"), (4, "emit"), (0, "stores")]
     print(f"kind={kind} p={prob} L={tlog or 'opt'}: ms per ablation (cumulative) and phase deltas", flush=True)
+    base = static_lds()
     for wg in wgs:
-        x = max(0, LDS_CU // wg - BASE - 64) if wg < 11 else 0
+        x = pad_for(wg, base)
         os.environ["FSEHIP_ENC_XLDS"] = str(x)
         prev, row = 0.0, []
         for dbg, name in abl:
@@ -40,7 +40,7 @@ def main():
             t = timeit(lambda: codec.compress_into(src, cb), reps=5)
             row.append(f"{name} {t:.3f} (+{t - prev:.3f})")
             prev = t
-        print(f"wg/cu={wg:2d} xlds={x:6d}  " + "  ".join(row), flush=True)
+        print(f"wg/cu={resident(base + x):2d} xlds={x:6d}  " + "  ".join(row), flush=True)
     os.environ["FSEHIP_ENC_XLDS"] = "0"
     os.environ["FSEHIP_DEBUG"] = "0"
 
