@@ -45,6 +45,7 @@ EXPORTS = (
     "fse_compress2_many", "fse_compress_many", "fsehip_compress_streams", "fsehip_stream_out_bytes",
     "fsehip_frame_bound", "fsehip_frame_read_header", "fsehip_frame_write_header",
     "fsehip_frame_compress", "fsehip_frame_decompress",
+    "fsehip_frame_decompress_ranges", "fsehip_frame_decompress_range",
 )
 
 STATUS = {
@@ -82,6 +83,11 @@ class FrameInfo(C.Structure):
                 ("flags", C.c_uint32), ("block_size", C.c_uint32), ("ckpt_interval", C.c_uint32),
                 ("n_blocks", C.c_uint32), ("reserved", C.c_uint32), ("n_total", C.c_uint64),
                 ("records_off", C.c_uint64)]
+
+
+class FrameRange(C.Structure):
+    """fsehip_frame_range: raw bytes [src_off, src_off + len) go to d_out + dst_off."""
+    _fields_ = [("src_off", C.c_uint64), ("len", C.c_uint64), ("dst_off", C.c_uint64)]
 
 
 class FrameParams(C.Structure):
@@ -197,6 +203,9 @@ def load() -> C.CDLL:
     lib.fsehip_frame_write_header.argtypes = [C.POINTER(FrameInfo), P]
     lib.fsehip_frame_compress.argtypes = [C.POINTER(FrameParams), P, u64, P, u64, P, P, P]
     lib.fsehip_frame_decompress.argtypes = [C.POINTER(FrameInfo), u32, P, u64, P, u64, P, P, P]
+    lib.fsehip_frame_decompress_ranges.argtypes = [C.POINTER(FrameInfo), u32, P, u64, C.POINTER(FrameRange), u32, P, u64,
+                                                   P, P, P]
+    lib.fsehip_frame_decompress_range.argtypes = [C.POINTER(FrameInfo), u32, P, u64, u64, u64, P, u64, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     H, NH = C.POINTER(Histogram), C.POINTER(NormHistogram)
     lib.histogram_new.argtypes = [P, sz, H]

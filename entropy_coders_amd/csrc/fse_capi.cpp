@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "../../include/fsehip.h"
+#include "fse_frame_plan.h"
 #include "fse_kernels.h"
 
 namespace {
@@ -48,7 +49,21 @@ enum {
     SCRATCH_FRAME_SLOTS = 7,  // the chunk's slots
     SCRATCH_FRAME_META = 8,   // checkpoints, comp_len, status, record type
     SCRATCH_FRAME_SCAN = 9,   // record offsets + the running frame offset
-    SCRATCH_KINDS = 10
+    // fsehip_frame_decompress_ranges
+    SCRATCH_FRAME_LIST = 10,    // the planner's lists and the per-listed-block results
+    SCRATCH_FRAME_BOUNCE = 11,  // a bounce chunk's decoded blocks
+    SCRATCH_KINDS = 12
+};
+// Pinned host staging for lists an asynchronous call uploads (the range
+// planner's).  A buffer is busy until the event recorded after its copy has
+// passed; a call takes a free one or adds one, so it never waits for the
+// stream.  At most kPinBufs per workspace: beyond that the oldest is waited for.
+constexpr int kPinBufs = 8;
+struct PinBuf {
+    void* p = nullptr;
+    uint64_t cap = 0;
+    hipEvent_t ev = nullptr;
+    bool busy = false;
 };
 struct Workspace {
     int dev;
@@ -61,6 +76,8 @@ struct Workspace {
     // retrying a multi-GiB hipMalloc on every call; cleared by
     // fsehip_release_workspace
     uint64_t failed[SCRATCH_KINDS] = {};
+    PinBuf pin[kPinBufs];
+    int pin_next = 0;  // the oldest busy buffer when all are busy
 };
 std::mutex g_ws_mu;
 std::vector<std::unique_ptr<Workspace>> g_ws;
@@ -106,6 +123,44 @@ struct Lease {
         }
         return ws->ptr[tag];
     }
+    // a pinned host buffer of `bytes` no pending copy reads; pin_sent() after its copy is enqueued
+    PinBuf* pin_get(uint64_t bytes) {
+        if (!ws) return nullptr;
+        PinBuf* pick = nullptr;
+        for (PinBuf& b : ws->pin) {
+            if (b.busy && hipEventQuery(b.ev) == hipSuccess) b.busy = false;
+            (void)hipGetLastError();  // hipErrorNotReady is no error
+            if (!b.busy && (!pick || (b.cap >= bytes && pick->cap < bytes))) pick = &b;
+        }
+        if (!pick) {
+            pick = &ws->pin[ws->pin_next];
+            ws->pin_next = (ws->pin_next + 1) % kPinBufs;
+            if (hipEventSynchronize(pick->ev) != hipSuccess) return nullptr;
+            pick->busy = false;
+        }
+        if (pick->cap < bytes) {
+            if (pick->p) (void)hipHostFree(pick->p);
+            pick->p = nullptr;
+            pick->cap = 0;
+            if (hipHostMalloc(&pick->p, bytes, hipHostMallocDefault) != hipSuccess) {
+                (void)hipGetLastError();
+                pick->p = nullptr;
+                return nullptr;
+            }
+            pick->cap = bytes;
+        }
+        if (!pick->ev && hipEventCreateWithFlags(&pick->ev, hipEventDisableTiming) != hipSuccess) return nullptr;
+        return pick;
+    }
+    bool pin_sent(PinBuf* b) {
+        if (hipEventRecord(b->ev, static_cast<hipStream_t>(ws->stream)) != hipSuccess) {
+            // the copy's end is unknown: wait for it here rather than hand the buffer out early
+            (void)hipStreamSynchronize(static_cast<hipStream_t>(ws->stream));
+            return false;
+        }
+        b->busy = true;
+        return true;
+    }
 };
 
 // Free every buffer of the matching workspaces (device < 0: all devices;
@@ -129,6 +184,7 @@ int release_workspaces(int device, void* stream, bool any_stream) {
         }
         bool any = false;
         for (int t = 0; t < SCRATCH_KINDS; ++t) any = any || w->ptr[t];
+        for (const PinBuf& b : w->pin) any = any || b.p;
         if (any && hipStreamSynchronize(static_cast<hipStream_t>(w->stream)) != hipSuccess) rc = FSE_ERR_HIP;
         for (int t = 0; t < SCRATCH_KINDS; ++t) {
             if (w->ptr[t] && hipFree(w->ptr[t]) != hipSuccess) rc = FSE_ERR_HIP;
@@ -136,6 +192,12 @@ int release_workspaces(int device, void* stream, bool any_stream) {
             w->bytes[t] = 0;
             w->failed[t] = 0;
         }
+        for (PinBuf& b : w->pin) {
+            if (b.p && hipHostFree(b.p) != hipSuccess) rc = FSE_ERR_HIP;
+            if (b.ev) (void)hipEventDestroy(b.ev);
+            b = PinBuf();
+        }
+        w->pin_next = 0;
     }
     (void)hipSetDevice(prev);
     return rc;
@@ -929,6 +991,161 @@ int fsehip_frame_decompress(const fsehip_frame_info* info, uint32_t chunk_blocks
         if (fsehip::launch_frame_merge(F, d_block_status, d_result, hs) != hipSuccess) return FSE_ERR_HIP;
     }
     return FSE_OK;
+}
+
+// Ranges.  The planner (fse_frame.cpp) turns the ranges into listed blocks,
+// direct runs and bounce chunks; its lists go to the device through pinned
+// staging in one copy.  LIST scratch, uploaded part first:
+//   pieces | range slots | listed blocks | bounce slots || record offsets |
+//   record type | comp_len | block status | a result pair the direct runs' merge counts into
+int fsehip_frame_decompress_ranges(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                                   uint64_t frame_len, const fsehip_frame_range* ranges, uint32_t n_ranges,
+                                   uint8_t* d_out, uint64_t out_cap, int32_t* d_range_status, int32_t* d_result,
+                                   fsehip_stream_t stream) {
+    if (!info || !d_frame || !d_result || (n_ranges && !ranges)) return FSE_ERR_BAD_ARG;
+    if (info->block_size > kMaxBlock) return FSE_ERR_UNSUPPORTED;
+    uint8_t hb[32];
+    fsehip::FrameHdr hdr;
+    if (fsehip_frame_write_header(info, hb) != FSE_OK) return FSE_ERR_BAD_ARG;
+    bool any = false;
+    for (uint32_t r = 0; r < n_ranges; ++r) any = any || ranges[r].len;
+    if (any && !d_out) return FSE_ERR_BAD_ARG;
+    const uint32_t bs = info->block_size, ns = info->nstates, ckpt = info->ckpt_interval;
+    const uint64_t n_blocks = info->n_blocks;
+    const uint64_t slot_bytes = fsehip_slot_bytes(bs, info->max_table_log);
+    const uint32_t cb_cap = frame_chunk_blocks(chunk_blocks, n_blocks, slot_bytes);
+    const uint64_t out_addr = reinterpret_cast<uintptr_t>(d_out);
+    // validation and planning are host work: both come before any device use
+    fsehip::RangePlan plan;
+    int rc = fsehip::frame_plan_ranges(info, cb_cap, out_addr, out_cap, ranges, n_ranges, &plan);
+    if (rc != FSE_OK) return rc;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    memcpy(hdr.w, hb, sizeof(hb));
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const fsehip_params bp{bs, 0, ckpt, info->max_table_log, ns};
+    const uint32_t spb = fsehip_sidecar_per_block_ns(bs, ckpt, ns);
+    // the chunk scratch holds the largest chunk this call runs, not chunk_blocks
+    uint64_t cb_use = std::min<uint64_t>(cb_cap, plan.bounce.size());
+    for (const fsehip::RangeRun& run : plan.runs) cb_use = std::max(cb_use, std::min<uint64_t>(cb_cap, run.n_blocks));
+    cb_use = std::max<uint64_t>(cb_use, 1u);
+    Lease lease(stream);
+    FrameScratch S = frame_scratch(lease, (uint32_t)cb_use, slot_bytes, spb, !plan.blocks.empty());
+    if (!S.ok) return FSE_ERR_HIP;
+    fsehip::FrameChunk& F = S.F;
+    F.frame = const_cast<uint8_t*>(d_frame);
+    F.frame_len = frame_len;
+    F.n_total = info->n_total;
+    F.block_size = bs;
+    F.ckpt_interval = ckpt;
+    F.nstates = ns;
+    F.n_blocks = (uint32_t)n_blocks;
+    F.raw = d_out;
+    if (fsehip::launch_frame_check(F, hdr, d_result, hs) != hipSuccess) return FSE_ERR_HIP;
+
+    fsehip::FrameRanges R{};
+    const uint64_t n_u = plan.blocks.size(), n_b = plan.bounce.size(), n_p = plan.bounce_piece.size();
+    if (n_u > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;
+    R.n_listed = (uint32_t)n_u;
+    R.out = d_out;
+    const uint64_t up_bytes = round_up(sizeof(fsehip::FramePiece) * n_p + 8ull * n_ranges + 4ull * n_u + 4ull * n_b, 8);
+    int32_t* run_result = nullptr;
+    if (n_ranges) {
+        uint8_t* list = static_cast<uint8_t*>(lease.get(SCRATCH_FRAME_LIST, up_bytes + 20ull * n_u + 8u));
+        PinBuf* pin = lease.pin_get(up_bytes);
+        if (!list || !pin) return FSE_ERR_HIP;
+        uint8_t* h = static_cast<uint8_t*>(pin->p);
+        fsehip::FramePiece* hp = reinterpret_cast<fsehip::FramePiece*>(h);
+        for (uint64_t k = 0; k < n_p; ++k) {
+            const fsehip::RangePiece& pc = plan.pieces[plan.bounce_piece[k]];
+            hp[k] = fsehip::FramePiece{pc.bounce, pc.in_off, pc.len, 0u, pc.dst_off};
+        }
+        uint32_t* hr = reinterpret_cast<uint32_t*>(hp + n_p);
+        for (uint32_t r = 0; r < n_ranges; ++r) {
+            hr[2u * r] = plan.range_slot[r];
+            hr[2u * r + 1u] = plan.range_blocks[r];
+        }
+        uint32_t* hbk = hr + 2ull * n_ranges;
+        if (n_u) memcpy(hbk, plan.blocks.data(), 4ull * n_u);
+        if (n_b) memcpy(hbk + n_u, plan.bounce.data(), 4ull * n_b);
+        if (hipMemcpyAsync(list, h, up_bytes, hipMemcpyHostToDevice, hs) != hipSuccess) {
+            (void)hipStreamSynchronize(hs);
+            return FSE_ERR_HIP;
+        }
+        if (!lease.pin_sent(pin)) return FSE_ERR_HIP;
+        R.pieces = reinterpret_cast<const fsehip::FramePiece*>(list);
+        R.range_slots = reinterpret_cast<const uint2*>(list + sizeof(fsehip::FramePiece) * n_p);
+        R.blocks = reinterpret_cast<const uint32_t*>(list + sizeof(fsehip::FramePiece) * n_p + 8ull * n_ranges);
+        R.bounce = R.blocks + n_u;
+        R.off = reinterpret_cast<uint64_t*>(list + up_bytes);
+        R.kind = reinterpret_cast<uint32_t*>(R.off + n_u);
+        R.clen = R.kind + n_u;
+        R.status = reinterpret_cast<int32_t*>(R.clen + n_u);
+        run_result = R.status + n_u;
+    }
+    if (n_b) {
+        R.raw_bounce = static_cast<uint8_t*>(lease.get(SCRATCH_FRAME_BOUNCE, std::min<uint64_t>(cb_cap, n_b) * bs));
+        if (!R.raw_bounce) return FSE_ERR_HIP;
+    }
+    if (fsehip::launch_frame_seek(F, R, hs) != hipSuccess) return FSE_ERR_HIP;
+    auto decode_chunk = [&](uint8_t* out, uint64_t chunk_total) {
+        // non-FSE blocks have comp_len 0: their table build fails and no decode kernel touches their output
+        return with_dtables_lease(&bp, F.slots, slot_bytes, F.comp_len, F.cb, stream, lease,
+                                  [&](const uint32_t* dt, const int32_t* dti, Lease& l) {
+                                      return decompress_impl(&bp, F.slots, slot_bytes, F.comp_len, F.sidecar, out,
+                                                             chunk_total, nullptr, F.status, nullptr, 0, stream, dt,
+                                                             dti, &l);
+                                  });
+    };
+    // the direct route: the chunk loop of fsehip_frame_decompress over a run's
+    // blocks, with F.raw shifted so that block b lands at its place in d_out
+    for (const fsehip::RangeRun& run : plan.runs) {
+        if (fsehip::launch_frame_seed(F, R, run.slot, hs) != hipSuccess) return FSE_ERR_HIP;
+        F.raw = reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(d_out) + run.dst_off -
+                                           (uint64_t)run.first_block * bs);
+        int32_t* st = reinterpret_cast<int32_t*>(reinterpret_cast<uintptr_t>(R.status) + 4ull * run.slot -
+                                                 4ull * run.first_block);
+        const uint64_t end = (uint64_t)run.first_block + run.n_blocks;
+        for (uint64_t c0 = run.first_block; c0 < end; c0 += cb_use) {
+            F.c0 = (uint32_t)c0;
+            F.cb = (uint32_t)std::min<uint64_t>(cb_use, end - c0);
+            const uint64_t chunk_total = std::min<uint64_t>((uint64_t)F.cb * bs, info->n_total - c0 * bs);
+            if (fsehip::launch_frame_scan(F, hs) != hipSuccess || fsehip::launch_frame_unpack(F, hs) != hipSuccess)
+                return FSE_ERR_HIP;
+            rc = decode_chunk(reinterpret_cast<uint8_t*>(reinterpret_cast<uintptr_t>(F.raw) + c0 * bs), chunk_total);
+            if (rc != FSE_OK) return rc;
+            if (fsehip::launch_frame_merge(F, st, run_result, hs) != hipSuccess) return FSE_ERR_HIP;
+        }
+    }
+    // the bounce route
+    F.raw = nullptr;
+    F.c0 = 0;
+    for (size_t c = 0; c + 1u < plan.chunk_start.size(); ++c) {
+        const uint32_t j0 = plan.chunk_start[c];
+        F.cb = plan.chunk_start[c + 1u] - j0;
+        const uint64_t last = plan.blocks[plan.bounce[j0 + F.cb - 1u]];
+        const uint64_t raw_last = std::min<uint64_t>(bs, info->n_total - last * bs);
+        if (fsehip::launch_frame_gather(F, R, j0, hs) != hipSuccess) return FSE_ERR_HIP;
+        rc = decode_chunk(R.raw_bounce, (uint64_t)(F.cb - 1u) * bs + raw_last);
+        if (rc != FSE_OK) return rc;
+        if (fsehip::launch_frame_gather_merge(F, R, j0, hs) != hipSuccess) return FSE_ERR_HIP;
+        uint32_t max_len = 0;
+        for (uint64_t p = plan.chunk_piece[c]; p < plan.chunk_piece[c + 1u]; ++p)
+            max_len = std::max(max_len, plan.pieces[plan.bounce_piece[p]].len);
+        for (uint64_t p = plan.chunk_piece[c]; p < plan.chunk_piece[c + 1u]; p += 1u << 30) {
+            const uint32_t np = (uint32_t)std::min<uint64_t>(1u << 30, plan.chunk_piece[c + 1u] - p);
+            if (fsehip::launch_frame_pieces(F, R, j0, p, np, max_len, hs) != hipSuccess) return FSE_ERR_HIP;
+        }
+    }
+    return fsehip::launch_frame_range_status(R, n_ranges, d_range_status, d_result, hs) == hipSuccess ? FSE_OK
+                                                                                                       : FSE_ERR_HIP;
+}
+
+int fsehip_frame_decompress_range(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                                  uint64_t frame_len, uint64_t src_off, uint64_t len, uint8_t* d_out, uint64_t out_cap,
+                                  int32_t* d_result, fsehip_stream_t stream) {
+    const fsehip_frame_range one{src_off, len, 0};
+    return fsehip_frame_decompress_ranges(info, chunk_blocks, d_frame, frame_len, &one, 1, d_out, out_cap, nullptr,
+                                          d_result, stream);
 }
 
 int fsehip_generate(int kind, double prob, uint64_t seed, uint32_t block_size, uint8_t* d_out, uint64_t n_total,

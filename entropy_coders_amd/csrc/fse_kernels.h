@@ -236,4 +236,44 @@ hipError_t launch_frame_scan(const FrameChunk& F, hipStream_t hs);
 hipError_t launch_frame_unpack(const FrameChunk& F, hipStream_t hs);
 hipError_t launch_frame_merge(const FrameChunk& F, int32_t* block_status, int32_t* result, hipStream_t hs);
 
+// Ranges (fsehip_frame_decompress_ranges).  The host planner's lists on the
+// device; a "slot" indexes the listed (covered) blocks, ascending.  The seek
+// kernel fills off / kind / clen per slot, the routes fill status per slot.
+struct FramePiece {
+    uint32_t bounce;   // index into FrameRanges::bounce
+    uint32_t in_off;   // first byte within the block
+    uint32_t len;
+    uint32_t pad;
+    uint64_t dst_off;  // from d_out
+};
+struct FrameRanges {
+    uint32_t n_listed;
+    const uint32_t* blocks;  // [n_listed] block numbers, ascending
+    uint64_t* off;           // [n_listed] record offsets (0: the frame failed its check)
+    uint32_t* kind;          // [n_listed] validated record type
+    uint32_t* clen;          // [n_listed] comp_len of an FSE record, else 0
+    int32_t* status;         // [n_listed] block status
+    const uint32_t* bounce;  // slots of the bounce route, ascending; a chunk is bounce[j0 .. j0 + F.cb)
+    const FramePiece* pieces;  // bounce pieces in bounce order
+    const uint2* range_slots;  // per range: first slot, slot count
+    uint8_t* raw_bounce;       // F.cb * block_size: where a bounce chunk is decoded
+    uint8_t* out;              // d_out
+};
+// record offsets, types and lengths of the listed blocks, by one pass over
+// the directory (after launch_frame_check: reads *F.base)
+hipError_t launch_frame_seek(const FrameChunk& F, const FrameRanges& R, hipStream_t hs);
+// bounce chunk at j0: FSE records of the listed blocks into F's slot scratch
+hipError_t launch_frame_gather(const FrameChunk& F, const FrameRanges& R, uint32_t j0, hipStream_t hs);
+// block statuses of the chunk (after its decode)
+hipError_t launch_frame_gather_merge(const FrameChunk& F, const FrameRanges& R, uint32_t j0, hipStream_t hs);
+// pieces [p0, p0 + np) of the chunk, none longer than max_len: RAW from the
+// record, RLE filled, FSE from the bounce
+hipError_t launch_frame_pieces(const FrameChunk& F, const FrameRanges& R, uint32_t j0, uint64_t p0, uint32_t np,
+                               uint32_t max_len, hipStream_t hs);
+// *F.base = R.off[slot]: seeds launch_frame_scan for a direct run
+hipError_t launch_frame_seed(const FrameChunk& F, const FrameRanges& R, uint32_t slot, hipStream_t hs);
+// range statuses from the block statuses; result[1] = ranges with a failed block
+hipError_t launch_frame_range_status(const FrameRanges& R, uint32_t n_ranges, int32_t* range_status, int32_t* result,
+                                     hipStream_t hs);
+
 }  // namespace fsehip

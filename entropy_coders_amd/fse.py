@@ -12,7 +12,7 @@ import threading
 import numpy as np
 
 from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, EncodeTable, FrameInfo,
-                   FrameParams, FseError, Histogram, NormHistogram, Params, check, load)
+                   FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, check, load)
 
 
 def _buf(data) -> np.ndarray:
@@ -722,6 +722,57 @@ class BlockCodec:
         check(int(result[0].item()), "frame")
         return out, status
 
+    @staticmethod
+    def frame_ranges(ranges):
+        """(src_off, len, dst_off) triples as the fsehip_frame_range array the
+        C call reads."""
+        arr = (FrameRange * max(len(ranges), 1))(*[FrameRange(int(s), int(ln), int(d)) for s, ln, d in ranges])
+        arr.empty = len(ranges) == 0
+        return arr
+
+    def decompress_frame_ranges_into(self, frame, info: FrameInfo, ranges, out, range_status, result,
+                                     chunk_blocks: int = 0) -> None:
+        """`fsehip_frame_decompress_ranges`, no synchronisation: `ranges` a
+        sequence of (src_off, len, dst_off), or what `frame_ranges` made of
+        one (a caller that repeats a call builds the array once); range r's
+        raw bytes go to out[dst_off: dst_off + len] (`out` a uint8 device
+        tensor, any alignment).  `range_status` len(ranges) int32 or None,
+        `result` two int32 (frame status, ranges with a failed block)."""
+        arr = ranges if isinstance(ranges, C.Array) else self.frame_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        check(self.lib.fsehip_frame_decompress_ranges(
+            C.byref(info), chunk_blocks, C.c_void_p(frame.data_ptr()), frame.numel(), arr, n,
+            C.c_void_p(out.data_ptr()), out.numel(),
+            C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_frame_decompress_ranges")
+
+    def decompress_frame_ranges(self, frame, ranges, chunk_blocks: int = 0):
+        """Decode the raw byte ranges [(src_off, len), ...] of a frame (a uint8
+        device tensor) without decoding the rest.  The ranges are packed back
+        to back into one uint8 tensor; returns (list of views of it, one per
+        range, and the int32 range statuses).  Raises FseError for a
+        frame-level error (BAD_FRAME)."""
+        t = self.torch
+        info = self.frame_info(frame)
+        packed, at = [], 0
+        for s, ln in ranges:
+            packed.append((s, ln, at))
+            at += ln
+        out = t.empty(at, dtype=t.uint8, device=self.device)
+        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_frame_ranges_into(frame, info, packed, out, status, result, chunk_blocks)
+        check(int(result[0].item()), "frame")
+        return [out[d: d + ln] for _, ln, d in packed], status
+
+    def decompress_frame_range(self, frame, offset: int, length: int, chunk_blocks: int = 0):
+        """Raw bytes [offset, offset + length) of a frame as a uint8 device
+        tensor; raises FseError for a frame-level error or with the status of
+        the first failed block the range touches."""
+        views, status = self.decompress_frame_ranges(frame, [(offset, length)], chunk_blocks)
+        check(int(status[0].item()), "frame range")
+        return views[0]
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -757,10 +808,23 @@ def frame_decompress(data, device=None) -> bytes:
     return out.cpu().numpy().tobytes()
 
 
+def frame_decompress_range(data, offset: int, length: int, device=None) -> bytes:
+    """Raw bytes [offset, offset + length) of a frame held in host memory;
+    raises FseError as BlockCodec.decompress_frame_range.  The whole frame is
+    uploaded: sending only the header, the directory and the records the
+    range needs is out of scope here."""
+    import torch
+
+    codec = BlockCodec(device=device)
+    BlockCodec.frame_info(_buf(data))  # not a frame: BAD_FRAME before any device work
+    frame = torch.from_numpy(_buf(data).copy()).to(codec.device)
+    return codec.decompress_frame_range(frame, offset, length).cpu().numpy().tobytes()
+
+
 __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStackWriter", "BitStreamReader", "BlockCodec", "DecodeTable", "EncodeTable", "FseError",
            "Histogram", "NormHistogram", "bitstack_read", "bitstack_write", "bitstream_read", "compress", "compress2",
            "compress2_log", "compress2_many", "compress_nh", "compress_streams", "decode_table_new", "decompress", "decompress2", "decompress2_many",
            "decompress_streams",
-           "encode_table_new", "frame_compress", "frame_decompress",
+           "encode_table_new", "frame_compress", "frame_decompress", "frame_decompress_range",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal"]

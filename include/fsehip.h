@@ -416,7 +416,23 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
  *                  8 * chunk_blocks + 8               record offsets and the
  *                                                     running frame offset,
  *                  plus the encode-spread / decode-table / deferred-symbol
- *                  entries above for a batch of chunk_blocks blocks.
+ *                  entries above for a batch of chunk_blocks blocks;
+ *   frame ranges   (fsehip_frame_decompress_ranges) the frame chunk entries
+ *                  above for the largest chunk the call runs (at most
+ *                  chunk_blocks blocks), plus
+ *                  chunk * block_size                 the bounce chunk's
+ *                                                     decoded blocks,
+ *                  8 per listed block                 record offsets (the
+ *                                                     seek pass keeps the
+ *                                                     covered blocks' only,
+ *                                                     not one per block of
+ *                                                     the frame),
+ *                  16 per listed block, 4 per bounced block, 24 per bounce
+ *                  piece, 8 per range + 8             block number, record
+ *                                                     type, comp_len, status
+ *                                                     and the planner's
+ *                                                     lists,
+ *                  and as many bytes of pinned host staging as the lists.
  * Growing a buffer synchronises the stream before freeing the old one.
  * First table build on a device (any encode or decode call): the library
  * first runs a ~1 ms synchronous self-check on the null stream (the lane
@@ -696,6 +712,77 @@ int fsehip_frame_compress(const fsehip_frame_params* p, const uint8_t* d_src, ui
 int fsehip_frame_decompress(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
                             uint64_t frame_len, uint8_t* d_out, uint64_t out_cap, int32_t* d_block_status,
                             int32_t* d_result, fsehip_stream_t stream);
+
+/* One byte range of a frame's raw content and where it goes. */
+typedef struct {
+    uint64_t src_off; /* first raw byte of the range */
+    uint64_t len;     /* bytes; 0 is valid */
+    uint64_t dst_off; /* the range goes to d_out + dst_off */
+} fsehip_frame_range;
+
+/* Decode byte ranges of a frame without decoding the rest of it: range r's
+ * bytes [src_off, src_off + len) of the raw content go to d_out + dst_off.
+ * `ranges` is a host array, read before the call returns.  d_frame, d_out,
+ * src_off, len and dst_off may have any byte alignment.  n_ranges == 0 and
+ * len == 0 are valid.  Source ranges may overlap or repeat; destinations of
+ * non-empty ranges may not overlap.
+ *
+ * The frame check of fsehip_frame_decompress runs first (header == info, the
+ * directory's record lengths end at frame_len): a frame that fails it gets
+ * d_result[0] = BAD_FRAME, every range status BAD_FRAME (empty ranges
+ * included, d_result[1] = n_ranges), and no byte of d_out is touched.
+ * Otherwise the stores are exactly the bytes [d_out + dst_off, d_out +
+ * dst_off + len) of each range, minus the portions that come from failed
+ * blocks: a block that fails (a bad directory entry or a decoder status, as
+ * in fsehip_frame_decompress) loses only its own bytes, in every range that
+ * touches it.  d_range_status (n_ranges entries, may be NULL): FSE_OK or the
+ * status of the lowest-numbered failed block the range touches.  d_result[0]
+ * = frame status, d_result[1] = ranges with a failed block.
+ *
+ * Work: only the header, the directory (up to the last covered block) and
+ * the records of covered blocks are read; blocks no range covers are never
+ * unpacked or decoded, so their records may hold anything as long as the
+ * directory's lengths still add up.  A host planner lists the covered blocks
+ * once each, and one directory pass (a seek kernel) gives their record
+ * offsets.  Two routes:
+ *   direct  a run of >= 4 whole blocks of one range whose destination start
+ *           is 16-byte aligned (the frame's last block counts as whole when
+ *           the range ends at n_total) goes through the chunk loop of
+ *           fsehip_frame_decompress with the output shifted, in place;
+ *   bounce  every other piece: the listed blocks' FSE records are gathered
+ *           into slot scratch and decoded, a chunk at a time, into a raw
+ *           bounce buffer, and a piece kernel (one workgroup per piece)
+ *           copies each piece to its destination; RAW pieces are copied and
+ *           RLE pieces filled straight from the record.
+ * A covered block is unpacked and decoded once per call, with one
+ * exception: a block that a direct run decodes in place for one range and of
+ * which another range (or the same source range sent to a second
+ * destination) needs a piece is decoded again on the bounce route.
+ *
+ * Chunks hold at most chunk_blocks blocks (0 = 4096, and few enough that
+ * the slots stay within 1 GiB); the chunk scratch is sized by the largest
+ * chunk the call runs, not by chunk_blocks.  The workspace entries are listed
+ * in the note at fsehip_decompress_blocks.  The lists travel through pinned
+ * host staging owned by the workspace (up to 8 buffers; with 8 earlier
+ * uploads of the stream still pending the call waits for the oldest).
+ * Asynchronous on `stream`, no host synchronisation except then and when the
+ * workspace grows; the call holds the stream's workspace throughout.
+ *
+ * Before any device use: BAD_ARG (a null info, d_frame, d_result, ranges
+ * with n_ranges > 0, or d_out with a non-empty range; an `info` that
+ * fsehip_frame_read_header would reject; src_off + len overflowing or past
+ * info->n_total; dst_off + len overflowing; overlapping destinations),
+ * DST_TOO_SMALL (dst_off + len > out_cap), UNSUPPORTED and NO_DEVICE as
+ * fsehip_frame_decompress. */
+int fsehip_frame_decompress_ranges(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                                   uint64_t frame_len, const fsehip_frame_range* ranges, uint32_t n_ranges,
+                                   uint8_t* d_out, uint64_t out_cap, int32_t* d_range_status, int32_t* d_result,
+                                   fsehip_stream_t stream);
+/* The one-range call with dst_off = 0 and no range status: d_result[1] != 0
+ * tells that a block of the range failed. */
+int fsehip_frame_decompress_range(const fsehip_frame_info* info, uint32_t chunk_blocks, const uint8_t* d_frame,
+                                  uint64_t frame_len, uint64_t src_off, uint64_t len, uint8_t* d_out, uint64_t out_cap,
+                                  int32_t* d_result, fsehip_stream_t stream);
 
 /* The bitstream as device passes over `count` fields (a prefix scan of the
  * widths places every field; HBM-bound).
