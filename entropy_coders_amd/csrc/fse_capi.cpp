@@ -59,6 +59,7 @@ enum {
 // passed; a call takes a free one or adds one, so it never waits for the
 // stream.  At most kPinBufs per workspace: beyond that the oldest is waited for.
 constexpr int kPinBufs = 8;
+constexpr uint64_t kPinMin = 64u << 10;  // smallest capacity of one
 struct PinBuf {
     void* p = nullptr;
     uint64_t cap = 0;
@@ -126,11 +127,21 @@ struct Lease {
     // a pinned host buffer of `bytes` no pending copy reads; pin_sent() after its copy is enqueued
     PinBuf* pin_get(uint64_t bytes) {
         if (!ws) return nullptr;
+        // among the free buffers: one that holds `bytes`, else one never
+        // allocated, else one to regrow.  hipHostFree waits for every stream
+        // of the device, so a regrow makes the call wait for the work queued
+        // before it, as a workspace buffer's growth does.
         PinBuf* pick = nullptr;
+        int best = -1;
         for (PinBuf& b : ws->pin) {
             if (b.busy && hipEventQuery(b.ev) == hipSuccess) b.busy = false;
             (void)hipGetLastError();  // hipErrorNotReady is no error
-            if (!b.busy && (!pick || (b.cap >= bytes && pick->cap < bytes))) pick = &b;
+            if (b.busy) continue;
+            const int rank = b.cap >= bytes ? 2 : !b.p ? 1 : 0;
+            if (rank > best) {
+                best = rank;
+                pick = &b;
+            }
         }
         if (!pick) {
             pick = &ws->pin[ws->pin_next];
@@ -142,12 +153,15 @@ struct Lease {
             if (pick->p) (void)hipHostFree(pick->p);
             pick->p = nullptr;
             pick->cap = 0;
-            if (hipHostMalloc(&pick->p, bytes, hipHostMallocDefault) != hipSuccess) {
+            // powers of two from kPinMin: lists of a few thousand ranges never regrow a buffer
+            uint64_t want = kPinMin;
+            while (want < bytes) want <<= 1;
+            if (hipHostMalloc(&pick->p, want, hipHostMallocDefault) != hipSuccess) {
                 (void)hipGetLastError();
                 pick->p = nullptr;
                 return nullptr;
             }
-            pick->cap = bytes;
+            pick->cap = want;
         }
         if (!pick->ev && hipEventCreateWithFlags(&pick->ev, hipEventDisableTiming) != hipSuccess) return nullptr;
         return pick;

@@ -432,7 +432,8 @@ int fsehip_compress_blocks(const fsehip_params* p, const uint8_t* d_src, uint64_
  *                                                     type, comp_len, status
  *                                                     and the planner's
  *                                                     lists,
- *                  and as many bytes of pinned host staging as the lists.
+ *                  and pinned host staging for the lists (64 KiB a buffer, or
+ *                  the next power of two that holds them).
  * Growing a buffer synchronises the stream before freeing the old one.
  * First table build on a device (any encode or decode call): the library
  * first runs a ~1 ms synchronous self-check on the null stream (the lane
@@ -763,8 +764,10 @@ typedef struct {
  * the slots stay within 1 GiB); the chunk scratch is sized by the largest
  * chunk the call runs, not by chunk_blocks.  The workspace entries are listed
  * in the note at fsehip_decompress_blocks.  The lists travel through pinned
- * host staging owned by the workspace (up to 8 buffers; with 8 earlier
- * uploads of the stream still pending the call waits for the oldest).
+ * host staging owned by the workspace (up to 8 buffers of 64 KiB, or of the
+ * next power of two that holds the lists; with 8 earlier uploads of the
+ * stream still pending the call waits for the oldest, and a call whose lists
+ * outgrow every free buffer regrows one, which waits for the device).
  * Asynchronous on `stream`, no host synchronisation except then and when the
  * workspace grows; the call holds the stream's workspace throughout.
  *
