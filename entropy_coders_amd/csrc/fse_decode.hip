@@ -224,6 +224,7 @@ __device__ __forceinline__ int32_t decode_segment1(WindowReader& br, uint32_t& s
 // ------------------------------------------------------------------------
 constexpr int32_t PAIR_MAX_BITS = 28;  // 2 x 14: the largest pair at the LDS-staged table logs
 struct LdsChain {
+    static constexpr bool SINGLE_STEP = false;  // segments are whole pairs
     int32_t pos, B;
     uint32_t whi, wlo, a0, a1;
     __device__ __forceinline__ void init(const uint32_t* pay, int32_t p, uint32_t s0, uint32_t s1) {
@@ -307,17 +308,88 @@ __device__ __forceinline__ void rows_transpose(uint32_t* w) {
         }
 }
 
-// Whole output groups of one chain per lane, wave-synchronous (every lane of
-// the wave runs ng_max iterations; a lane decodes only its first my_ng),
-// stored through rows_transpose: obase[k] / ong[k] are the piece base and
-// group count of lane (k, column) -- the owner of this lane's slot k.
+// The first `nb` bytes (1..16) of a 16-byte chunk t[] from the lane's own
+// registers: one 16-byte store, or dword stores and byte stores for the last
+// 1..3.  No byte at or past dst + nb is touched (the next block's bytes
+// belong to another workgroup).  dst is 16-byte aligned.
+__device__ __forceinline__ void store_chunk(uint8_t* __restrict__ dst, const uint32_t* t, uint32_t nb) {
+    if (nb >= 16u) {
+        __builtin_nontemporal_store(u32x4{t[0], t[1], t[2], t[3]}, reinterpret_cast<u32x4*>(dst));
+        return;
+    }
+#pragma unroll
+    for (uint32_t i = 0; i < 4u; ++i) {
+        if (nb >= 4u * i + 4u) {
+            *reinterpret_cast<uint32_t*>(dst + 4u * i) = t[i];
+        } else if (nb > 4u * i) {
+            dst[4u * i] = (uint8_t)t[i];
+            if (nb > 4u * i + 1u) dst[4u * i + 1u] = (uint8_t)(t[i] >> 8);
+            if (nb > 4u * i + 2u) dst[4u * i + 2u] = (uint8_t)(t[i] >> 16);
+        }
+    }
+}
+
+// Output groups of one chain per lane, wave-synchronous (every lane of the
+// wave runs ng_max iterations), stored through rows_transpose: obase[k] /
+// ong[k] are the offset in `out` and the whole-group count of the piece of
+// lane (k, column) -- the owner of this lane's slot k; own_off is the lane's
+// own.  A lane decodes its my_ng whole groups and then, in iteration my_ng,
+// the `tail` bytes its segment has beyond them (0..63: the block's last
+// segment, or every segment when checkpoints are closer than a group) while
+// the wave's other lanes decode a whole group: at C2 the last segment's lane
+// does its 31 pairs beside its wave's second group (before, it ran them
+// alone, pair by pair, after the groups, with the other seven waves waiting
+// at the final barrier).  An iteration with such a lane (a wave-uniform
+// test) goes 16 bytes at a time in a rolled loop, every pair predicated on
+// the lane's count, so no pair past a segment's end is decoded and the
+// chain ends in the state after the segment's last pair.  A lane with a
+// tail stores each chunk itself from its own registers (store_chunk); the
+// whole pieces of the wave's other lanes are collected chunk by chunk and
+// go through the transpose like every other iteration's.  (Unrolled over
+// the 32 pairs the predicated iteration took 84 VGPRs against 64, 2
+// workgroups per CU instead of 3; rolled it takes 79.  Storing the whole
+// pieces of that iteration as four separate 16-byte chunks per lane instead
+// measured C2 decode 0.50 -> 0.70 ms: a sixteenth of the output in partial
+// non-temporal writes.  profiles/lane_serial/.)
 template <class Chain, class Tab>
-__device__ __forceinline__ void run_groups_tx(Chain& c, uint32_t my_ng, uint32_t ng_max, const uint32_t* pay,
-                                              const Tab& dtb, uint8_t* const* obase, const uint32_t* ong,
-                                              uint32_t row) {
+__device__ __forceinline__ void run_groups_tx(Chain& c, uint32_t my_ng, uint32_t tail, uint32_t ng_max,
+                                              const uint32_t* pay, const Tab& dtb, uint8_t* __restrict__ out,
+                                              const uint32_t* obase, const uint32_t* ong, uint32_t row,
+                                              uint32_t own_off) {
     for (uint32_t g = 0; g < ng_max; ++g) {
         uint32_t w[DEC_GROUP / 2u];
-        if (g < my_ng) {
+        const bool part = g == my_ng && tail != 0u;
+        if (__ballot(part) != 0ull) {
+            // bytes of this iteration's piece: the chain's pair() makes two,
+            // a 1-state segment may end on a single step
+            const uint32_t nb = g < my_ng ? 2u * DEC_GROUP : part ? tail : 0u;
+#pragma unroll
+            for (uint32_t j = 0; j < DEC_GROUP / 2u; ++j) w[j] = 0;
+#pragma unroll 1
+            for (uint32_t q = 0; q < 4u; ++q) {
+                const uint32_t lim = nb > 16u * q ? nb - 16u * q : 0u;  // bytes from this chunk on
+                const uint32_t cnt = lim >> 1;
+                uint32_t t[4];
+#pragma unroll
+                for (uint32_t j = 0; j < 8u; j += 2u) {
+                    uint32_t x = 0;
+                    if (j < cnt) x = c.pair(pay, dtb);
+                    if (j + 1u < cnt) x = __builtin_amdgcn_perm(c.pair(pay, dtb), x, 0x05040100u);
+                    if constexpr (Chain::SINGLE_STEP) {
+                        if ((lim & 1u) && j == cnt) x = c.step_sym(pay, dtb);
+                        if ((lim & 1u) && j + 1u == cnt) x |= c.step_sym(pay, dtb) << 16;
+                    }
+                    t[j >> 1] = x;
+                }
+                if (part && lim) store_chunk(out + (own_off + g * 2u * DEC_GROUP + 16u * q), t, lim);
+                // the chunk enters the piece from the top: after the four
+                // trips chunk q sits in w[4q .. 4q + 3]
+#pragma unroll
+                for (uint32_t i = 0; i < DEC_GROUP / 2u - 4u; ++i) w[i] = w[i + 4u];
+#pragma unroll
+                for (uint32_t i = 0; i < 4u; ++i) w[DEC_GROUP / 2u - 4u + i] = t[i];
+            }
+        } else if (g < my_ng) {
 #pragma unroll
             for (uint32_t j = 0; j < DEC_GROUP; j += 2u) w[j >> 1] = two_pairs(c, pay, dtb);
         } else {
@@ -330,9 +402,10 @@ __device__ __forceinline__ void run_groups_tx(Chain& c, uint32_t my_ng, uint32_t
         // (C3 0.95 -> 0.91 ms, C2 decode 0.60 -> 0.57 ms, same box)
 #pragma unroll
         for (int k = 0; k < 4; ++k)
-            if (g < ong[k])
-                __builtin_nontemporal_store(u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]},
-                                            reinterpret_cast<u32x4*>(obase[k] + g * 2u * DEC_GROUP + 16u * row));
+            if (g < ong[k])  // (a 32-bit offset from the block's scalar base)
+                __builtin_nontemporal_store(
+                    u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]},
+                    reinterpret_cast<u32x4*>(out + (obase[k] + g * 2u * DEC_GROUP + 16u * row)));
     }
 }
 
@@ -433,8 +506,12 @@ struct LdsChain1 {
     }
 };
 struct Chain1x2 {
+    static constexpr bool SINGLE_STEP = true;  // a segment may hold an odd count of symbols
     LdsChain1 c;
     __device__ __forceinline__ uint32_t pair(const uint32_t* pay, const uint8_t* dtb) { return c.pair(pay, dtb); }
+    __device__ __forceinline__ uint32_t step_sym(const uint32_t* pay, const uint8_t* dtb) {
+        return dte_sym(c.step(pay, dtb));
+    }
 };
 
 // Steps [p, p1) of one 1-state segment; the last segment then emits the
@@ -596,8 +673,9 @@ __device__ __forceinline__ void decode_pre_block(const DecParams& P, Smem& sm, c
     }
     if (NS == 2 && !BIG && in_lds) {
         // One segment per lane, every lane of a wave in step, output pieces
-        // stored through the row transpose (run_groups_tx); then each lane's
-        // tail pairs and, for the last segment, the block's end.
+        // stored through the row transpose (run_groups_tx), a segment's pairs
+        // beyond its whole groups included; then, for the last segment, the
+        // block's end.
         for (; base0 < nseg; base0 += NT) {
             const uint32_t seg = base0 + seg_of<NT>(tid);
             bool act = seg < nseg;
@@ -618,21 +696,22 @@ __device__ __forceinline__ void decode_pre_block(const DecParams& P, Smem& sm, c
                 }
             }
             const uint32_t my_ng = act ? (p1 - p0) / DEC_GROUP : 0u;
-            const uint32_t ng_max = wave_max(my_ng);
+            const uint32_t tail = act ? 2u * ((p1 - p0) % DEC_GROUP) : 0u;  // bytes beyond the whole groups
+            const uint32_t ng_max = wave_max(my_ng + (tail ? 1u : 0u));
             if (ng_max) {
-                uint8_t* obase[4];
+                uint32_t obase[4];
                 uint32_t ong[4];
 #pragma unroll
                 for (uint32_t k = 0; k < 4; ++k) {
                     const uint32_t os = base0 + seg_of<NT>((tid & ~63u) + 16u * k + (tid & 15u));
                     const uint32_t oq = os * I;
                     ong[k] = os < nseg ? (min(oq + I, Pm) - oq) / DEC_GROUP : 0u;
-                    obase[k] = out + 2u * oq;
+                    obase[k] = 2u * oq;
                 }
-                run_groups_tx(c, my_ng, ng_max, sm.pay, dtb, obase, ong, (tid >> 4) & 3u);
+                run_groups_tx(c, my_ng, tail, ng_max, sm.pay, dtb, out, obase, ong, (tid >> 4) & 3u, 2u * p0);
             }
-            if (act) {
-                r = run_chain(c, sm.pay, dtb, p0 + my_ng * DEC_GROUP, p1, lastseg, n, Pm, out, hdr_bits);
+            if (act) {  // every pair is decoded: only the block's end is left, for the last segment
+                r = run_chain(c, sm.pay, dtb, p1, p1, lastseg, n, Pm, out, hdr_bits);
                 if (r == FSE_OK && !lastseg && !ckpt_match(en, hdr_bits, smask, c.pos, c.s0() << 2, c.s1() << 2))
                     r = FSE_ERR_BAD_SIDECAR;
             }
@@ -662,21 +741,22 @@ __device__ __forceinline__ void decode_pre_block(const DecParams& P, Smem& sm, c
                 }
             }
             const uint32_t my_ng = act ? (p1 - p0) / G1 : 0u;
-            const uint32_t ng_max = wave_max(my_ng);
+            const uint32_t tail = act ? (p1 - p0) % G1 : 0u;  // symbols = bytes beyond the whole groups
+            const uint32_t ng_max = wave_max(my_ng + (tail ? 1u : 0u));
             if (ng_max) {
-                uint8_t* obase[4];
+                uint32_t obase[4];
                 uint32_t ong[4];
 #pragma unroll
                 for (uint32_t k = 0; k < 4; ++k) {
                     const uint32_t os = base0 + seg_of<NT>((tid & ~63u) + 16u * k + (tid & 15u));
                     const uint32_t oq = os * I;
                     ong[k] = os < nseg ? (min(oq + I, Pm) - oq) / G1 : 0u;
-                    obase[k] = out + oq;
+                    obase[k] = oq;
                 }
-                run_groups_tx(c, my_ng, ng_max, sm.pay, dtb, obase, ong, (tid >> 4) & 3u);
+                run_groups_tx(c, my_ng, tail, ng_max, sm.pay, dtb, out, obase, ong, (tid >> 4) & 3u, p0);
             }
-            if (act) {
-                r = run_chain1(c.c, sm.pay, dtb, p0 + my_ng * G1, p1, lastseg, n, out, hdr_bits);
+            if (act) {  // every step is decoded: only the final state's symbol is left, for the last segment
+                r = run_chain1(c.c, sm.pay, dtb, p1, p1, lastseg, n, out, hdr_bits);
                 if (r == FSE_OK && !lastseg && !ckpt_match(en, hdr_bits, smask, c.c.pos, c.c.a, 0u))
                     r = FSE_ERR_BAD_SIDECAR;
             }
@@ -743,8 +823,20 @@ __device__ __forceinline__ void decode_pre_block(const DecParams& P, Smem& sm, c
 // one after the other, so a batch with few or no deferred blocks costs a few
 // microseconds instead of a full-grid launch of empty workgroups (~0.03 ms
 // per GiB).
+// Waves per SIMD that the workgroups a CU's 160 KiB of LDS holds come to:
+// the register allocator is held to that occupancy (80 VGPRs for the three
+// 512-thread workgroups of the 44 KiB stage), as it otherwise spends
+// registers on scheduling freedom that costs a resident workgroup.
+template <class Smem>
+constexpr uint32_t lds_waves_per_simd(uint32_t nw) {
+    const uint32_t w = (160u << 10) / (uint32_t)sizeof(Smem) * nw / 4u;
+    return w < 1u ? 1u : w > 8u ? 8u : w;
+}
+
 template <int LMAX, uint32_t PMAX, int NS, int PASS, uint32_t NT = 256u>
-__global__ __launch_bounds__(NT) void decode_pre_kernel(DecParams P) {
+__global__ __launch_bounds__(NT) __attribute__((amdgpu_waves_per_eu(
+    lds_waves_per_simd<PreSmem<LMAX, (LMAX > 14) ? 16u : PMAX, NT / 64u>>(NT / 64u)))) void
+decode_pre_kernel(DecParams P) {
     constexpr bool BIG = LMAX > 14;
     constexpr uint32_t NW = NT / 64u;
     __shared__ PreSmem<LMAX, BIG ? 16u : PMAX, NW> sm;
