@@ -677,17 +677,14 @@ int fo_decompress2_n(const uint8_t* src, size_t n, uint8_t* dst, size_t raw_len)
     return decompress2_impl(src, n, dst, raw_len, &out_len, raw_len);
 }
 
-/* fse_compress (1 state), lib.rs:112-143 */
-int fo_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
-                uint64_t* payload_bits) {
-    fo_norm nh;
-    int rc = fo_norm_new(src, n, &nh); /* 114 */
-    if (rc) return rc;
+/* fse_compress body after the histogram, lib.rs:115-143 */
+static int compress1_body(const uint8_t* src, size_t n, const fo_norm* nh, uint8_t* dst,
+                          size_t cap, size_t* out_len, uint64_t* payload_bits) {
     size_t hlen;
-    rc = fo_header_write(&nh, dst, cap, &hlen); /* 115 */
+    int rc = fo_header_write(nh, dst, cap, &hlen); /* 115 */
     if (rc) return rc;
     static __thread fo_ctable ct;
-    rc = fo_build_ctable(&nh, &ct);
+    rc = fo_build_ctable(nh, &ct);
     if (rc) return rc;
     bw_t w;
     bw_init(&w, dst, cap, hlen);
@@ -710,6 +707,34 @@ int fo_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* 
     *out_len = bw_finish_bytes(&w);
     if (payload_bits) *payload_bits = bw_pos(&w) - (uint64_t)hlen * 8u;
     return FSE_OK;
+}
+
+/* fse_compress (1 state), lib.rs:112-143 */
+int fo_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap, size_t* out_len,
+                uint64_t* payload_bits) {
+    fo_norm nh;
+    int rc = fo_norm_new(src, n, &nh); /* 114 */
+    if (rc) return rc;
+    return compress1_body(src, n, &nh, dst, cap, out_len, payload_bits);
+}
+
+/* fse_compress with an explicit table log: Histogram::new(src).normalize(log2)
+ * (histogram.rs:18-66, 95-155: clamp to 5..15, raise to ilog2(table_len - 1)
+ * + 2) in place of NormHistogram::new at lib.rs:114, then lib.rs:115-143.
+ * normalize itself accepts a 1-byte input; it stays TOO_SHORT here, as under
+ * NormHistogram::new (histogram.rs:272), so that this entry refuses exactly
+ * what fse_compress refuses. */
+int fo_compress_log(const uint8_t* src, size_t n, uint32_t log2, uint8_t* dst, size_t cap,
+                    size_t* out_len, uint64_t* payload_bits) {
+    fo_hist h;
+    int rc = fo_hist_count(src, n, &h);
+    if (rc) return rc;
+    if (n == 0) return FSE_ERR_EMPTY;
+    fo_norm nh;
+    rc = fo_normalize(&h, log2, &nh, NULL); /* ALL_ZERO_SYMBOL0, CURSED */
+    if (rc) return rc;
+    if (n < 2) return FSE_ERR_TOO_SHORT;
+    return compress1_body(src, n, &nh, dst, cap, out_len, payload_bits);
 }
 
 /* fse_decompress (1 state), lib.rs:187-211 */

@@ -101,6 +101,10 @@ int fo_decompress2(const uint8_t* src, size_t n, uint8_t* dst, size_t cap,
 int fo_decompress2_n(const uint8_t* src, size_t n, uint8_t* dst, size_t raw_len);
 int fo_compress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap,
                 size_t* out_len, uint64_t* payload_bits);
+/* compress with an explicit table log: Histogram::new(src).normalize(L)
+ * then the fse_compress body (lib.rs:115-143).                            */
+int fo_compress_log(const uint8_t* src, size_t n, uint32_t log2, uint8_t* dst,
+                    size_t cap, size_t* out_len, uint64_t* payload_bits);
 int fo_decompress(const uint8_t* src, size_t n, uint8_t* dst, size_t cap,
                   size_t* out_len);
 

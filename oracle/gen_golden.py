@@ -62,25 +62,44 @@ CASES = [
     ("onestate_odd_777", 0, 0.3, 16, 777, None, 1),
 ]
 
+# The 1-state coder (fse_compress, lib.rs:112-143) at a forced table log:
+# Histogram::new(src).normalize(L) in place of NormHistogram::new, which never
+# picks a log above 11.  At L = 15 the lone seed is the last byte: 251 occurs
+# in none of the generators, so it occurs once: norm -1 from 32 KiB on, and 8
+# (a power of two, which also stays inside new_first_symbol's table, on another
+# symbol's state) at 4 KiB; the unpatched block is the reference's panic.  Written to
+# golden_onestate_log_v1.* (golden_v1.* stays as it is).
+ONESTATE_LOG_CASES = [
+    ("os_skew077_L5_4k", 0, 0.77, 0x5EED0300, 4096, 5, 1),
+    ("os_lut0155_L8_8k", 0, 0.155, 0x5EED0300, 8192, 8, 1),
+    ("os_uniform240_L12_16k", 2, 0.0, 0x5EED0300, 16384, 12, 1),
+    ("os_lut0155_L13_64k", 0, 0.155, 0x5EED0300, 65536, 13, 1),
+    ("os_geometric_L14_odd", 1, 0.5, 0x5EED0300, 40001, 14, 1),
+    ("os_lut0155_L15_rare_last", 0, 0.155, 0x5EED0300, 65536, 15, 1, {65535: 251}),
+    ("os_uniform240_L15_rare_last_4k", 2, 0.0, 0x5EED0300, 4096, 15, 1, {4095: 251}),
+    ("os_lut0155_L15_encoder_init", 0, 0.155, 0x5EED0300, 4096, 15, 1),
+]
+
 
 def _spec_compress(data: bytes, log2, fmt):
     if fmt == 1:
-        return S.compress(data)
+        return S.compress(data, log2)
     return S.compress2(data, log2)
 
 
-def main() -> None:
-    os.makedirs(OUT, exist_ok=True)
+def _cases(cases):
+    """(arrays, manifest entries) of a case list: every output from the C
+    oracle, re-derived by the spec."""
     arrays: dict[str, np.ndarray] = {}
-    manifest = {"generator": "oracle/gen_golden.py", "cases": []}
-    for name, kind, prob, seed, n, log2, fmt, *patch in CASES:
+    entries = []
+    for name, kind, prob, seed, n, log2, fmt, *patch in cases:
         src = O.generate(kind, prob, seed, 0, n)
         assert S.generate(kind, prob, seed, 0, n) == src.tobytes(), name
         for i, v in (patch[0] if patch else {}).items():
             src[i] = v
         try:
             if fmt == 1:
-                comp, bits = O.compress(src)
+                comp, bits = O.compress(src, log2)
             else:
                 comp, bits = O.compress2(src, log2)
         except O.OracleError as e:  # a reference panic: recorded as its status
@@ -90,7 +109,7 @@ def main() -> None:
             except S.SpecError as se:
                 assert str(se) == e.code, (name, str(se), e.code)
             arrays[name + "__src"] = src
-            manifest["cases"].append({"name": name, "kind": kind, "prob": prob, "seed": seed, "n": n,
+            entries.append({"name": name, "kind": kind, "prob": prob, "seed": seed, "n": n,
                                       "log2": log2, "format": fmt, "status": e.code,
                                       "patch": {str(k): v for k, v in (patch[0] if patch else {}).items()}})
             print(f"{name:24s} n={n:6d} status={e.code}")
@@ -106,13 +125,20 @@ def main() -> None:
         assert dec == src.tobytes() or log2 == 15, name
         arrays[name + "__src"] = src
         arrays[name + "__comp"] = np.frombuffer(comp, dtype=np.uint8)
-        manifest["cases"].append({
+        entries.append({
             "name": name, "kind": kind, "prob": prob, "seed": seed, "n": n, "log2": log2,
             "format": fmt, "payload_bits": bits, "comp_len": len(comp),
             "sha256_comp": hashlib.sha256(comp).hexdigest(), "roundtrip": dec == src.tobytes(),
             "patch": {str(k): v for k, v in (patch[0] if patch else {}).items()},
         })
         print(f"{name:24s} n={n:6d} comp={len(comp):6d} bits={bits}")
+    return arrays, entries
+
+
+def main() -> None:
+    os.makedirs(OUT, exist_ok=True)
+    arrays, entries = _cases(CASES)
+    manifest = {"generator": "oracle/gen_golden.py", "cases": entries}
 
     # 1 MiB of C2 data as 16 x 64 KiB blocks: digests only (inputs regenerate).
     digests = []
@@ -131,6 +157,15 @@ def main() -> None:
     np.savez_compressed(os.path.join(OUT, "golden_v1.npz"), **arrays)
     with open(os.path.join(OUT, "golden_v1.json"), "w") as f:
         json.dump(manifest, f, indent=1)
+
+    arrays, entries = _cases(ONESTATE_LOG_CASES)
+    for case in entries:  # the spec's decoder reads what the C decoder reads
+        if "status" not in case:
+            comp = arrays[case["name"] + "__comp"].tobytes()
+            assert S.decompress(comp) == O.decompress(comp) and len(O.decompress(comp)) == case["n"], case["name"]
+    np.savez_compressed(os.path.join(OUT, "golden_onestate_log_v1.npz"), **arrays)
+    with open(os.path.join(OUT, "golden_onestate_log_v1.json"), "w") as f:
+        json.dump({"generator": "oracle/gen_golden.py", "cases": entries}, f, indent=1)
     print("wrote", OUT)
 
 

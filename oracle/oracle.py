@@ -66,8 +66,9 @@ def lib():
         _lib.fo_generate.restype = None
         for name in ("fo_compress2", "fo_compress"):
             getattr(_lib, name).argtypes = [P, sz, P, sz, C.POINTER(sz), C.POINTER(C.c_uint64)]
-        _lib.fo_compress2_log.argtypes = [P, sz, C.c_uint32, P, sz, C.POINTER(sz),
-                                          C.POINTER(C.c_uint64)]
+        for name in ("fo_compress2_log", "fo_compress_log"):
+            getattr(_lib, name).argtypes = [P, sz, C.c_uint32, P, sz, C.POINTER(sz),
+                                            C.POINTER(C.c_uint64)]
         for name in ("fo_decompress2", "fo_decompress"):
             getattr(_lib, name).argtypes = [P, sz, P, sz, C.POINTER(sz)]
         _lib.fo_decompress2_n.argtypes = [P, sz, P, sz]
@@ -129,13 +130,20 @@ def compress2(src, log2: int | None = None) -> tuple[bytes, int]:
     return dst[: out_len.value].tobytes(), bits.value
 
 
-def compress(src) -> tuple[bytes, int]:
+def compress(src, log2: int | None = None) -> tuple[bytes, int]:
+    """fse_compress (lib.rs:112-143); with log2, Histogram::normalize(log2) in
+    place of NormHistogram::new (fo_compress_log)."""
     a = _u8(src)
     cap = compress_bound(len(a))
     dst = np.zeros(cap, dtype=np.uint8)
     out_len = C.c_size_t(0)
     bits = C.c_uint64(0)
-    _check(lib().fo_compress(_ptr(a), len(a), _ptr(dst), cap, C.byref(out_len), C.byref(bits)))
+    if log2 is None:
+        rc = lib().fo_compress(_ptr(a), len(a), _ptr(dst), cap, C.byref(out_len), C.byref(bits))
+    else:
+        rc = lib().fo_compress_log(_ptr(a), len(a), log2, _ptr(dst), cap, C.byref(out_len),
+                                   C.byref(bits))
+    _check(rc)
     return dst[: out_len.value].tobytes(), bits.value
 
 

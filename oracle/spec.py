@@ -452,18 +452,26 @@ def compress2(src: bytes, log2: int | None = None) -> tuple[bytes, int]:
     return head + sink.to_bytes(), len(sink.bits)
 
 
-def compress_headerless(src: bytes):
+def compress_headerless(src: bytes, log2: int | None = None):
     """The crate's test-module fse_compress (fse.rs:394-421): the 1-state
     stream of lib.rs:112-143 with no header in front (the caller keeps the
-    NormHistogram).  Returns (norm, L, table_len, payload, payload bits)."""
+    NormHistogram).  Returns (norm, L, table_len, payload, payload bits).
+    log2=None uses NormHistogram::new; a number takes its place in
+    Histogram::normalize (histogram.rs:95), which clamps and raises it.  A
+    1-byte input stays TOO_SHORT either way (histogram.rs:272 panics only under
+    NormHistogram::new; the forced log refuses what fse_compress refuses)."""
     counts, size, tl = histogram(src)
     if size == 0:
         raise SpecError("EMPTY")
     if tl == 1:
         raise SpecError("ALL_ZERO_SYMBOL0")
+    if log2 is None:
+        if size == 1:
+            raise SpecError("TOO_SHORT")
+        log2 = optimal_log2(size, tl)
+    norm, L, _ = normalize(counts, size, tl, log2)
     if size == 1:
         raise SpecError("TOO_SHORT")
-    norm, L, _ = normalize(counts, size, tl, optimal_log2(size, tl))
     tab = encode_table(norm, L, tl)
     sink = BitSink()
     n = len(src)
@@ -480,10 +488,10 @@ def compress_headerless(src: bytes):
     return norm, L, tl, sink.to_bytes(), len(sink.bits)
 
 
-def compress(src: bytes) -> tuple[bytes, int]:
+def compress(src: bytes, log2: int | None = None) -> tuple[bytes, int]:
     """fse_compress, one state (lib.rs:112-143): the header (hist.write) and,
-    from the next byte on, the headerless stream."""
-    norm, L, tl, payload, bits = compress_headerless(src)
+    from the next byte on, the headerless stream; log2 as in compress_headerless."""
+    norm, L, tl, payload, bits = compress_headerless(src, log2)
     return header_write(norm, L, tl) + payload, bits
 
 

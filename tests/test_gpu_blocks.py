@@ -399,10 +399,9 @@ def test_lds_stage_decode_table_logs_13_14(torch_cuda, L, nstates, ckpt):
     cb = codec.compress(src)
     torch.cuda.synchronize()
     assert int(cb["status"].abs().max()) == 0, cb["status"].cpu().numpy()
-    for b in (0, 1, 5):  # (the reference's 1-state fse_compress has no table-log argument)
-        want = O.compress2(host[b * B:(b + 1) * B], L)[0] if nstates == 2 else O.compress(host[b * B:(b + 1) * B])[0]
-        if nstates == 2:
-            assert codec.block_bytes(cb, b) == want, b
+    for b in (0, 1, 5):
+        want = (O.compress2 if nstates == 2 else O.compress)(host[b * B:(b + 1) * B], L)[0]
+        assert codec.block_bytes(cb, b) == want, b
     lens = cb["comp_len"].cpu().numpy()
     assert lens.max() > 44 * 1024 and lens.min() < 44 * 1024  # both passes run
     for side in (True, False):

@@ -120,7 +120,7 @@ def test_corpus_has_all_three_types(corpora):
     assert R.types_of(R.build_frame(corpora[1], BLOCK, CKPT, 2))[-1] == R.RAW  # the 1-byte tail: TOO_SHORT
 
 
-# 1-state at table_log 13 is left out: the oracle's fse_compress takes no table log
+# (1-state at table logs 12 and 13: tests/test_gpu_onestate_logs.py)
 FORMATS = [(2, CKPT, 0), (2, 0, 0), (2, CKPT, 13), (2, 0, 13), (1, CKPT, 0), (1, 0, 0)]
 
 

@@ -62,17 +62,27 @@ def test_random_batch_regressions(torch_cuda, seed, case):
     _random_batch(torch_cuda, seed, case, draw=1)
 
 
+# draw 3: the 1-state format at the 2-state draws' table logs (the oracle's
+# fse_compress with an explicit log, fo_compress_log)
+@pytest.mark.parametrize("case", range(16))
+def test_random_batches_onestate_logs(torch_cuda, case):
+    _random_batch(torch_cuda, 0xF0330, case, draw=3)
+
+
 def draw_case(seed, case, draw=2):
     """The batch of (seed, case): (nstates, block, table_log, ckpt, sizes,
     blocks).  draw 1: the lists of the sweeps that found REGRESSIONS; draw 2
     adds 128 KiB blocks (the windowed reader above the 66 KiB stage) and 8..32
-    checkpoints (several segment rounds per workgroup)."""
+    checkpoints (several segment rounds per workgroup); draw 3 is draw 2 with
+    every case 1-state and its table log from the 2-state list."""
     rng = np.random.default_rng(seed + case)
     nstates = int(rng.choice([1, 2]))
+    if draw == 3:
+        nstates = 1
     block = int(rng.choice([512, 1040, 4096, 20000, 65536] if draw == 1 else [512, 1040, 4096, 20000, 65536, 65536, 131072]))
     nblocks = int(rng.integers(1, 9))
     last = int(rng.integers(2, block + 1))
-    table_log = 0 if nstates == 1 else int(rng.choice([0, 0, 5, 7, 9, 11, 12, 13, 14, 15]))
+    table_log = 0 if nstates == 1 and draw != 3 else int(rng.choice([0, 0, 5, 7, 9, 11, 12, 13, 14, 15]))
     if draw == 1:
         ckpt = int(rng.choice([0, 64, 128, 256]))
     else:
@@ -84,7 +94,7 @@ def draw_case(seed, case, draw=2):
 
 def _random_batch(torch_cuda, seed, case, draw=2):
     torch = torch_cuda
-    from entropy_coders_amd import BlockCodec
+    from entropy_coders_amd import BlockCodec, FseError
     from entropy_coders_amd._lib import STATUS
 
     nstates, block, table_log, ckpt, sizes, blocks = draw_case(seed, case, draw)
@@ -95,10 +105,16 @@ def _random_batch(torch_cuda, seed, case, draw=2):
     src = torch.from_numpy(host).cuda()
     cb = codec.compress(src)
     routes = [("serial", codec.decompress(cb, use_sidecar=False))]
+    rebuilt = None
     if ckpt:
         routes.append(("sidecar", codec.decompress(cb)))
-        rebuilt = codec.build_sidecar(cb)
-        routes.append(("rebuild", rebuilt[::2]))
+        if nstates == 1 and codec.max_table_log > 12:  # fsehip_build_sidecar: 1-state classes 13..15 record nothing
+            with pytest.raises(FseError) as unsup:
+                codec.build_sidecar(cb)
+            assert unsup.value.code == "UNSUPPORTED"
+        else:
+            rebuilt = codec.build_sidecar(cb)
+            routes.append(("rebuild", rebuilt[::2]))
     torch.cuda.synchronize()
     est = cb["status"].cpu().numpy()
     spb = codec.side_per_block
@@ -108,7 +124,7 @@ def _random_batch(torch_cuda, seed, case, draw=2):
             if nstates == 2:
                 want, wbits = O.compress2(s, table_log or None)
             else:
-                want, wbits = O.compress(s)
+                want, wbits = O.compress(s, table_log or None)
         except O.OracleError as e:
             assert STATUS.get(int(est[b])) == e.code, what
             for name, (out, st) in routes:
@@ -124,11 +140,14 @@ def _random_batch(torch_cuda, seed, case, draw=2):
         ref = s
         if nstates == 2 and table_log == 15:
             ref = np.frombuffer(O.decompress2(want, raw_len=len(s)), np.uint8)
+        elif table_log == 15 and len(set(s.tolist())) > 1:  # 1-state: the crate's decoder ends after n symbols
+            ref = np.frombuffer(O.decompress(want), np.uint8)
+            assert len(ref) == len(s), what
         lo = b * block
         for name, (out, st) in routes:
             assert int(st[b]) == 0, (name, what, STATUS.get(int(st[b])))
             assert np.array_equal(out[lo: lo + len(s)].cpu().numpy(), ref), (name, what)
-        if ckpt:
+        if rebuilt is not None:
             side = rebuilt[1]
             assert torch.equal(side[b * spb: (b + 1) * spb], cb["sidecar"][b * spb: (b + 1) * spb]), what
     assert n == sum(sizes)
@@ -180,6 +199,13 @@ def test_decompress_streams_regressions(torch_cuda, seed):
     _streams_case(1, seed, draw=1)
 
 
+@pytest.mark.parametrize("host", [False, True], ids=["decompress_streams", "decompress_many"])
+def test_streams_onestate_logs(torch_cuda, host):
+    """Draw 3: 1-state streams at the 2-state draw's table logs (5..15), one
+    set per entry point."""
+    _streams_case(1, 0x57AE + 330000 + int(host), draw=3, host=host)
+
+
 @pytest.mark.parametrize("rep", range(int(os.environ.get("FSEHIP_FUZZ_STREAM_REPS", 1))))
 @pytest.mark.parametrize("nstates", [2, 1])
 def test_decompress_many_random(torch_cuda, nstates, rep):
@@ -193,7 +219,7 @@ def test_decompress_many_random(torch_cuda, nstates, rep):
 def _streams_case(nstates, seed, draw, host=False):
     """60 crate streams of one seed.  draw 1: the lists of the sweep that found
     the regressions above; draw 2 adds table logs 5..8, 14, 15, longer streams
-    and other strides.  host: through fse_decompress2_many (any table log in
+    and other strides; draw 3 gives 1-state streams draw 2's logs.  host: through fse_decompress2_many (any table log in
     one call) instead of fsehip_decompress_streams at each bound."""
     from entropy_coders_amd import decompress2_many, decompress_streams
 
@@ -202,14 +228,14 @@ def _streams_case(nstates, seed, draw, host=False):
     streams, logs = [], []
     for i in range(60):
         s = _block(rng, int(rng.integers(2, 20000 if draw == 1 else 48000)))
-        if nstates == 1:
+        if nstates == 1 and draw != 3:
             L = 0
         elif draw == 1:
             L = int(rng.choice([0, 0, 0, 9, 12, 13]))
         else:
             L = int(rng.choice([0, 0, 0, 5, 8, 9, 11, 12, 13, 14, 15]))
         try:
-            comp = O.compress2(s, L or None)[0] if nstates == 2 else O.compress(s)[0]
+            comp = O.compress2(s, L or None)[0] if nstates == 2 else O.compress(s, L or None)[0]
         except O.OracleError:
             continue
         comp = bytearray(comp)

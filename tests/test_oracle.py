@@ -235,14 +235,19 @@ def test_checkpoints1_consistent():
 def test_oracle_matches_spec_random(case):
     """The two independent restatements agree on seeded random blocks (the
     fuzz generator's distributions, lengths up to 3 KiB, table logs 5..15,
-    both formats), including the error statuses and the decode."""
+    both formats), including the error statuses and the decode.  The 1-state
+    format runs at NormHistogram::new's log and at a log of its own draw."""
     from test_gpu_fuzz import _block
 
     rng = np.random.default_rng(0x5BEC + case)
     src = _block(rng, int(rng.integers(2, 3073))).tobytes()
     log2 = [None, 5, 8, 11, 12, 15][int(rng.integers(0, 6))]
-    for enc_o, enc_s, dec_s in ((lambda b: O.compress2(b, log2), lambda b: S.compress2(b, log2), S.decompress2),
-                                (O.compress, S.compress, S.decompress)):
+    # (a generator of its own: the blocks and 2-state logs above stay as they were)
+    log1 = [0, 5, 7, 9, 11, 12, 13, 14, 15, 20][int(np.random.default_rng(0x15BEC + case).integers(0, 10))]
+    for enc_o, enc_s, dec_s, dec_o in (
+            (lambda b: O.compress2(b, log2), lambda b: S.compress2(b, log2), S.decompress2, O.decompress2),
+            (O.compress, S.compress, S.decompress, O.decompress),
+            (lambda b: O.compress(b, log1), lambda b: S.compress(b, log1), S.decompress, O.decompress)):
         try:
             want = enc_s(src)
         except S.SpecError as e:
@@ -253,7 +258,175 @@ def test_oracle_matches_spec_random(case):
         got = enc_o(src)
         assert got == want, case
         if len(set(src)) > 1:
-            assert dec_s(want[0]) == src, case
+            L = (want[0][0] & 15) + 5
+            if L < 15 or dec_o is O.decompress2:
+                assert dec_s(want[0]) == src, case
+            else:  # a 1-state stream at L = 15: the crate's own decode, n bytes
+                assert dec_s(want[0]) == dec_o(want[0]) and len(dec_o(want[0])) == len(src), case
+
+
+# ---- the 1-state coder at a forced table log (Histogram::normalize(L) + lib.rs:115-143)
+ONESTATE_LOGS = [0, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 20]
+ONESTATE_SHAPES = ["lut0155", "lut077", "uniform240", "geometric", "sparse"]
+RARE = 251  # in none of the shapes: where it is patched in it occurs once
+
+
+def onestate_source(shape, n, seed=0x5EED0300):
+    if shape == "sparse":  # 5 symbols far apart: long zero runs in the header, table_len 255
+        rng = np.random.default_rng(seed + n)
+        return np.array([1, 40, 41, 200, 254], np.uint8)[rng.choice(5, n, p=[0.6, 0.2, 0.1, 0.07, 0.03])]
+    kind, prob = {"lut0155": (0, 0.155), "lut077": (0, 0.77), "uniform240": (2, 0.0), "geometric": (1, 0.5)}[shape]
+    return O.generate(kind, prob, seed, 0, n)
+
+
+def _both(src, log2):
+    """compress(src, log2) on both restatements: (bytes, payload bits), or the
+    status name both report."""
+    try:
+        want = S.compress(src, log2)
+    except S.SpecError as e:
+        with pytest.raises(O.OracleError) as ei:
+            O.compress(src, log2)
+        assert ei.value.code == e.code, (log2, e.code, ei.value.code)
+        return e.code
+    assert O.compress(src, log2) == want, log2
+    return want
+
+
+@pytest.mark.parametrize("n", [2, 3, 5, 64, 777, 4096, 20001])
+@pytest.mark.parametrize("shape", ONESTATE_SHAPES)
+def test_onestate_forced_log_matches_spec(shape, n):
+    """fo_compress_log against spec.compress(src, L): bytes, payload bits and
+    status at every log, then both decoders on every accepted stream.  Below
+    L = 15 the round trip is the source; at 15 the crate's own decode (n bytes,
+    DESIGN.md section 3).  At requests >= 15 the block is also run with the rare
+    last byte, which new_first_symbol accepts."""
+    base = onestate_source(shape, n)
+    accepted = set()
+    for log2 in ONESTATE_LOGS:
+        variants = [base]
+        if log2 >= 15:
+            variants.append(base.copy())
+            variants[1][-1] = RARE
+        for src in variants:
+            src = src.tobytes()
+            want = _both(src, log2)
+            if isinstance(want, str):
+                assert want in ("ALL_ZERO_SYMBOL0", "ENCODER_INIT", "CURSED"), (log2, want)
+                continue
+            comp, bits = want
+            L = (comp[0] & 15) + 5
+            tl = max(src) + 1
+            assert L == max(min(max(log2, 5), 15), (tl - 1).bit_length() + 1), (log2, L)  # histogram.rs:96-98
+            accepted.add(L)
+            if len(set(src)) == 1:  # the crate's decoder never ends on it
+                for dec, err in ((O.decompress, O.OracleError), (S.decompress, S.SpecError)):
+                    with pytest.raises(err) as e:
+                        dec(comp)
+                    assert e.value.code == "SINGLE_SYMBOL"
+                continue
+            dec = O.decompress(comp)
+            assert S.decompress(comp) == dec, (log2, L)
+            assert len(dec) == n, (log2, L)
+            if L < 15:
+                assert dec == src, (log2, L)
+    assert accepted or not base.any(), (shape, n)  # (three bytes of the skewed shape are all zero)
+    if n in (64, 4096, 20001):  # the rare last byte's norm is a power of two there: inside the table at 15
+        assert 15 in accepted, (shape, n, sorted(accepted))
+
+
+@pytest.mark.parametrize("shape", ONESTATE_SHAPES)
+def test_onestate_log_none_is_fse_compress(shape):
+    """log2=None is NormHistogram::new, on both restatements and in the
+    headerless variant; so is its optimal_log2 given as a number."""
+    for n in (2, 3, 64, 777, 4096):
+        src = onestate_source(shape, n)
+        b = src.tobytes()
+        try:
+            old = O.compress(src)
+        except O.OracleError as e:  # (three bytes of the skewed shape: all zero)
+            with pytest.raises(O.OracleError) as e2:
+                O.compress(src, None)
+            with pytest.raises(S.SpecError) as e3:
+                S.compress(b, None)
+            assert e2.value.code == e3.value.code == e.code
+            continue
+        assert O.compress(src, None) == old and S.compress(b) == old and S.compress(b, None) == old
+        assert S.compress_headerless(b, None) == S.compress_headerless(b)
+        L = O.optimal_log2(O.hist_count(src))
+        assert O.compress(src, L) == old and S.compress(b, L) == old
+        assert S.compress_headerless(b, L) == S.compress_headerless(b)
+
+
+def test_onestate_log_error_codes():
+    for data, code in ((b"", "EMPTY"), (b"\x07", "TOO_SHORT"), (bytes(100), "ALL_ZERO_SYMBOL0")):
+        for L in (0, 9, 13, 15):
+            assert _both(data, L) == code, (data[:2], L)
+    assert _both(b"\x01\x02\x03", 15) == "ENCODER_INIT"  # a seed of norm 10923: its index wraps out of the table
+
+
+@pytest.fixture(scope="module")
+def golden_onestate_log():
+    import json
+    import os
+
+    gdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    with open(os.path.join(gdir, "golden_onestate_log_v1.json")) as f:
+        manifest = json.load(f)
+    return manifest, np.load(os.path.join(gdir, "golden_onestate_log_v1.npz"), allow_pickle=False)
+
+
+def test_golden_onestate_log_vectors(golden_onestate_log):
+    """The committed 1-state forced-log vectors (oracle/gen_golden.py,
+    ONESTATE_LOG_CASES): the C oracle reproduces every stream and status."""
+    import os
+
+    manifest, arrays = golden_onestate_log
+    seen, statuses = set(), set()
+    for case in manifest["cases"]:
+        assert case["format"] == 1 and 4096 <= case["n"] <= 65536
+        src = arrays[case["name"] + "__src"]
+        regen = O.generate(case["kind"], case["prob"], case["seed"], 0, case["n"])
+        for i, v in case["patch"].items():
+            regen[int(i)] = v
+        assert np.array_equal(regen, src)
+        if "status" in case:
+            with pytest.raises(O.OracleError) as e:
+                O.compress(src, case["log2"])
+            assert e.value.code == case["status"], case["name"]
+            statuses.add(case["status"])
+            continue
+        comp = arrays[case["name"] + "__comp"].tobytes()
+        assert hashlib.sha256(comp).hexdigest() == case["sha256_comp"]
+        assert O.compress(src, case["log2"]) == (comp, case["payload_bits"]), case["name"]
+        L = (comp[0] & 15) + 5
+        assert L == case["log2"]
+        seen.add(L)
+        dec = O.decompress(comp)
+        assert len(dec) == case["n"] and (dec == src.tobytes()) == case["roundtrip"], case["name"]
+        assert case["roundtrip"] or L == 15
+        if L == 15:
+            assert src[-1] == RARE
+    assert seen == {5, 8, 12, 13, 14, 15} and statuses == {"ENCODER_INIT"}
+    gdir = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+    assert (os.path.getsize(os.path.join(gdir, "golden_onestate_log_v1.npz"))
+            < os.path.getsize(os.path.join(gdir, "golden_v1.npz")))
+
+
+@pytest.mark.parametrize("name", ["os_skew077_L5_4k", "os_uniform240_L15_rare_last_4k", "os_lut0155_L15_encoder_init"])
+def test_golden_onestate_log_spec(golden_onestate_log, name):
+    """The spec re-derives the small vectors (gen_golden.py checks them all)."""
+    manifest, arrays = golden_onestate_log
+    case = next(c for c in manifest["cases"] if c["name"] == name)
+    src = arrays[name + "__src"].tobytes()
+    if "status" in case:
+        with pytest.raises(S.SpecError) as e:
+            S.compress(src, case["log2"])
+        assert e.value.code == case["status"]
+        return
+    comp = arrays[name + "__comp"].tobytes()
+    assert S.compress(src, case["log2"]) == (comp, case["payload_bits"])
+    assert S.decompress(comp) == O.decompress(comp)
 
 
 @pytest.mark.parametrize("prob,n", [(0.2, 1 << 15), (0.5, 333), (0.05, 4096), (0.77, 1001)])
