@@ -1,6 +1,6 @@
 // fse_frame_plan.h -- the host planner of fsehip_frame_decompress_ranges
 // (fsehip.h section 2b; defined in fse_frame.cpp).  Plain C++ with no HIP
-// include: fse_capi.cpp uses it, and tests/native/frame_ranges_fuzz.cpp
+// include: fse_capi_frame.cpp uses it, and tests/native/frame_ranges_fuzz.cpp
 // builds it with g++ alone.  Not part of the public ABI.
 #pragma once
 #include <stdint.h>

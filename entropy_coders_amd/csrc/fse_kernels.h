@@ -1,4 +1,4 @@
-// fse_kernels.h -- internal launch interface between the C ABI (fse_capi.cpp)
+// fse_kernels.h -- internal launch interface between the C ABI (fse_capi*.cpp)
 // and the gfx950 kernels (fse_kernels.hip).  Not part of the public ABI.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -150,7 +150,7 @@ def test_reference_kats_through_hip_normalize(torch_cuda):
 @pytest.mark.parametrize("nstates", [2, 1])
 def test_host_calls_past_the_pinned_window(torch_cuda, nstates):
     """Per-call entry points whose compressed and decoded bytes exceed the 4 MiB
-    pinned return window (fse_capi.cpp kPinOut): the head comes back through
+    pinned return window (fse_workspace.h kPinOut): the head comes back through
     pinned memory, the rest by a device-to-host copy; bytes equal the oracle's
     and the stream decodes back exactly (near-uniform data, ~1 B per byte)."""
     from entropy_coders_amd import compress, compress2, decompress, decompress2

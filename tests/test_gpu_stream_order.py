@@ -43,7 +43,7 @@ N_BLOCKS, TAIL = 40, 333
 SRC_POISON = 7          # the constant byte an encoder's source holds before the upload
 A5, F32, F64 = FILL["uint8"], FILL["int32"], FILL["int64"]
 GATE_FACTOR, GATE_FLOOR_MS, GATE_CAP_MS = 20, 50.0, 1000.0
-PIN_BUFS = 8            # kPinBufs (csrc/fse_capi.cpp): staging buffers of the ranges call per workspace
+PIN_BUFS = 8            # kPinBufs (csrc/fse_workspace.h): staging buffers of the ranges call per workspace
 
 
 @pytest.fixture(scope="module")
