@@ -46,6 +46,8 @@ EXPORTS = (
     "fsehip_frame_bound", "fsehip_frame_read_header", "fsehip_frame_write_header",
     "fsehip_frame_compress", "fsehip_frame_decompress",
     "fsehip_frame_decompress_ranges", "fsehip_frame_decompress_range",
+    "norm_histogram_try_from", "fsehip_shared_table_bytes", "fsehip_shared_table_build", "fsehip_shared_out_bytes",
+    "fsehip_compress_shared", "fsehip_decompress_shared",
 )
 
 STATUS = {
@@ -53,7 +55,7 @@ STATUS = {
     -5: "BAD_HEADER", -6: "NO_MARKER", -7: "DST_TOO_SMALL", -8: "TABLELOG_RANGE",
     -9: "CURSED", -10: "BAD_TABLE", -11: "BAD_ARG", -12: "HIP", -13: "LENGTH_MISMATCH",
     -14: "UNSUPPORTED", -15: "NO_DEVICE", -16: "BAD_SIDECAR", -17: "ENCODER_INIT",
-    -18: "EOF", -19: "BAD_FRAME",
+    -18: "EOF", -19: "BAD_FRAME", -20: "SYMBOL_NOT_IN_TABLE",
 }
 
 
@@ -207,6 +209,14 @@ def load() -> C.CDLL:
                                                    P, P, P]
     lib.fsehip_frame_decompress_range.argtypes = [C.POINTER(FrameInfo), u32, P, u64, u64, u64, P, u64, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
+    lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
+    lib.fsehip_shared_table_bytes.argtypes = []
+    lib.fsehip_shared_table_bytes.restype = u64
+    lib.fsehip_shared_table_build.argtypes = [P, P, P, P]
+    lib.fsehip_shared_out_bytes.argtypes = [u32, u32]
+    lib.fsehip_shared_out_bytes.restype = u64
+    lib.fsehip_compress_shared.argtypes = [u32, P, P, P, u32, P, P, P, P, P]
+    lib.fsehip_decompress_shared.argtypes = [u32, P, P, P, u32, P, P, P, P, P]
     H, NH = C.POINTER(Histogram), C.POINTER(NormHistogram)
     lib.histogram_new.argtypes = [P, sz, H]
     lib.histogram_normalize.argtypes = [H, u32, NH]

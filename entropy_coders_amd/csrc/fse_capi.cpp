@@ -479,9 +479,12 @@ int fsehip_rank_fallbacks(int device, uint32_t counts[3], int reset) {
     int prev = 0;
     if (hipGetDevice(&prev) != hipSuccess || hipSetDevice(device) != hipSuccess) return FSE_ERR_NO_DEVICE;
     const bool r = reset != 0;
+    uint32_t shared = 0;  // the shared-table images count with the table calls
     const bool ok = fsehip::rank_fallbacks_enc(&counts[0], r) == hipSuccess &&
                     fsehip::rank_fallbacks_dec(&counts[1], r) == hipSuccess &&
-                    fsehip::rank_fallbacks_tab(&counts[2], r) == hipSuccess;
+                    fsehip::rank_fallbacks_tab(&counts[2], r) == hipSuccess &&
+                    fsehip::rank_fallbacks_shared(&shared, r) == hipSuccess;
+    counts[2] += shared;
     (void)hipSetDevice(prev);
     return ok ? FSE_OK : FSE_ERR_HIP;
 }

@@ -197,6 +197,27 @@ hipError_t launch_copy(const uint8_t* src, const uint64_t* src_off, const uint32
 hipError_t launch_stream_offsets(const uint32_t* lens, uint32_t n, uint64_t* offsets, uint64_t* total,
                                  hipStream_t hs);
 
+// Shared-table coding (fsehip.h section 2c; fse_shared.hip): one device image
+// of both tables for table logs <= SHARED_LMAX, and one lane per message.
+constexpr uint32_t SHARED_LMAX = 12;
+constexpr uint32_t SHARED_BYTES = 64u + 256u * 8u + (2u << SHARED_LMAX) + (4u << SHARED_LMAX);
+struct SharedParams {
+    uint32_t nstates;  // 2 or 1
+    const uint8_t* table;  // the image
+    const uint8_t* in;     // encode: the messages; decode: the payloads (desc: src_off / src_len)
+    const fsehip_stream_desc* desc;
+    uint32_t n;
+    uint8_t* out;  // regions out_off / out_cap
+    uint32_t* len;   // comp_len / out_len
+    uint32_t* bits;  // encode: payload bits, or nullptr
+    const uint32_t* raw_len;  // decode: known lengths, or nullptr
+    int32_t* status;
+};
+hipError_t launch_shared_build(const fse_norm_histogram* nh, uint8_t* image, int32_t* status, hipStream_t s);
+hipError_t launch_shared_encode(const SharedParams& P, hipStream_t s);
+hipError_t launch_shared_decode(const SharedParams& P, hipStream_t s);
+hipError_t rank_fallbacks_shared(uint32_t* out, bool reset);  // counted with rank_fallbacks_tab
+
 // The frame (fsehip.h section 2b; fse_frame.hip).  One call works on the
 // blocks [c0, c0 + cb) of the frame -- a chunk -- with chunk-local scratch
 // arrays (index i = b - c0): the encoder's / decoder's slots, comp_len,

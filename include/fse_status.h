@@ -69,5 +69,10 @@
  * bytes, n_blocks != ceil(n_total / block_size), a directory that does not
  * add up to the frame's length, or (per block) an invalid directory entry.  */
 #define FSE_ERR_BAD_FRAME (-19)
+/* Shared-table coding (fsehip.h section 2c): a byte of the message has no
+ * slot in the caller's table -- its count is 0 or it lies at or past
+ * table_len.  The crate's Encoder::encode indexes its tables unchecked there
+ * (fse.rs:231-238).                                                          */
+#define FSE_ERR_SYMBOL_NOT_IN_TABLE (-20)
 
 #endif

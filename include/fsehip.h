@@ -787,6 +787,109 @@ int fsehip_frame_decompress_range(const fsehip_frame_info* info, uint32_t chunk_
                                   uint64_t frame_len, uint64_t src_off, uint64_t len, uint8_t* d_out, uint64_t out_cap,
                                   int32_t* d_result, fsehip_stream_t stream);
 
+/* ------------------------------------------------------------------------
+ * (2c) Shared-table coding: many small messages against one caller's table
+ *
+ * The crate's `pub mod fse` lets a caller code any number of messages against
+ * one table, with no header in front: EncodeTable::new(&NormHistogram),
+ * Encoder::{new_first_symbol, encode_raw, encode, finish}, DecodeTable::new,
+ * Decoder::{new, decode_symbol, finish} (fse.rs:86-386; its own tests do so,
+ * fse.rs:394-434).  Here that is one table image on the device and two
+ * batched calls.  There is no new format -- a message's payload is
+ *   nstates 2: the body of fse_compress2 from BitStackWriter::new on
+ *              (lib.rs:151-182), decoded by the loop of lib.rs:222-247;
+ *   nstates 1: the headerless stream of fse.rs:394-421 (= lib.rs:118-142),
+ *              decoded by the loop of lib.rs:187-211;
+ * so with the message's own normalised histogram as the table, the payload is
+ * the crate's stream minus its header bytes.  Small records gain twice: no
+ * table build and no header per message (a 512-byte message against a table
+ * trained on a sample: DESIGN.md section 5).
+ * ------------------------------------------------------------------------ */
+
+/* `impl TryFrom<[i32; 256]> for NormHistogram` (histogram.rs:508-536), with
+ * its quirks: the sum of |x| must be a power of two (log2 of it is the table
+ * log, whatever its value -- a log outside 5..15 is refused later, by the
+ * table build), and table_len = 1 + the last non-zero index.  Err(()) and the
+ * all-zero table (the crate's 0.ilog2() panic) are FSE_ERR_BAD_TABLE.  Host
+ * only, no device. */
+int norm_histogram_try_from(const int32_t table[256], fse_norm_histogram* out);
+
+/* EncodeTable::new + DecodeTable::new (fse.rs:88-189, 269-338) of the
+ * NormHistogram at d_nh (device memory) as one opaque image of
+ * fsehip_shared_table_bytes() bytes at d_table (16-byte aligned): the encode
+ * stateTable and symbol transforms, the decode table, which symbols have a
+ * slot, the table log and a validity word.  Table logs 5..12.  *d_status:
+ * FSE_OK; UNSUPPORTED for a log of 13..15; TABLELOG_RANGE outside 5..15;
+ * BAD_TABLE for table_len outside 1..256, an entry below -1, counts (-1 as 1)
+ * that do not sum to 2^log2 or a spread that does not close (fse.rs:151 /
+ * 326).  A failed build leaves the image marked invalid: every message coded
+ * with it gets BAD_TABLE and nothing is indexed with its contents.  The image
+ * may be copied and used on any stream after the build.  Asynchronous; BAD_ARG
+ * (a null or misaligned pointer) and NO_DEVICE before any device use. */
+uint64_t fsehip_shared_table_bytes(void);
+int fsehip_shared_table_build(const fse_norm_histogram* d_nh, uint8_t* d_table, int32_t* d_status,
+                              fsehip_stream_t stream);
+
+/* An output capacity that holds the payload of any message of src_len bytes
+ * at that table log (clamped to 5..12): src_len * L + 2 L + 1 bits, rounded
+ * up to 16 bytes. */
+uint64_t fsehip_shared_out_bytes(uint32_t src_len, uint32_t table_log);
+
+/* Encode n_msgs messages against the image d_table, one lane per message.
+ * Message i is the src_len bytes at d_src + src_off; its payload goes to
+ * d_out + out_off, at most out_cap bytes (fsehip_stream_desc and the memory
+ * rules of fsehip_compress_streams: reads are exactly [src_off, src_off +
+ * src_len); stores only inside [out_off, out_off + out_cap), whatever the
+ * status; bytes of a region beyond d_comp_len[i] are unspecified; regions do
+ * not overlap; d_table, d_src and d_out 16-byte aligned).
+ * d_comp_len[i] = payload bytes, d_payload_bits[i] (may be NULL) = its bits
+ * with the marker (the crate's return value); both 0 for a message that
+ * failed.  d_status[i], the first that applies:
+ *   BAD_TABLE     the image is invalid;
+ *   BAD_ARG       src_off or out_off is not a multiple of 16;
+ *   EMPTY         src_len 0;
+ *   TOO_SHORT     src_len 1 at nstates 2 (at nstates 1 one byte is valid:
+ *                 the seed, finish and the marker);
+ *   UNSUPPORTED   src_len above 65,536: a lane's serial chain would run for
+ *                 milliseconds; long messages belong on fsehip_compress_streams;
+ *   SYMBOL_NOT_IN_TABLE  a byte whose count is 0 or that lies at or past
+ *                 table_len (the crate indexes unchecked there, fse.rs:231-238);
+ *   DST_TOO_SMALL exactly when the payload exceeds out_cap.
+ * Asynchronous on `stream`; no workspace.  n_msgs == 0 returns FSE_OK and does
+ * nothing; a null pointer, nstates > 2 (0 = 2) or a misaligned base is
+ * BAD_ARG, n_msgs > 2^24 UNSUPPORTED, before any device use; otherwise
+ * NO_DEVICE or HIP. */
+int fsehip_compress_shared(uint32_t nstates, const uint8_t* d_table, const uint8_t* d_src,
+                           const fsehip_stream_desc* d_desc, uint32_t n_msgs, uint8_t* d_out, uint32_t* d_comp_len,
+                           uint32_t* d_payload_bits, int32_t* d_status, fsehip_stream_t stream);
+
+/* Decode n_msgs payloads against the image d_table, one lane per message.
+ * Payload i is the src_len bytes at d_in + src_off; its bytes go to d_out +
+ * out_off, at most out_cap; d_out_len[i] = bytes decoded (0 for a message
+ * that failed).  d_raw_len (may be NULL) gives each message's raw length:
+ * then the crate's loop runs with that limit, a single-symbol table decodes,
+ * and a payload that does not end with that many bytes is LENGTH_MISMATCH
+ * (the block decoders stop at the raw length whatever follows; here the
+ * payload must end there too: no bit left, and no step of the encoder undone
+ * beyond it.  Only steps that cost no bit -- a symbol above half the table --
+ * cannot be told from the end); without it the loop ends where the crate's
+ * does, within out_cap.  d_status[i], the first that
+ * applies: BAD_TABLE, BAD_ARG (as above), EMPTY (src_len 0), NO_MARKER (a zero
+ * last byte), DST_TOO_SMALL (a raw length above out_cap), LENGTH_MISMATCH (a
+ * raw length below 2 at nstates 2), SINGLE_SYMBOL (no lengths and a table of
+ * one symbol: the crate would decode forever), TOO_SHORT (no room for the
+ * states), then what the loop finds: LENGTH_MISMATCH with lengths,
+ * DST_TOO_SMALL without.
+ * Reads: no byte outside the payload (whole dwords from its end downwards, a
+ * last partial dword bytewise).  Stores: 16-byte groups inside the region, the
+ * last partial group bytewise, never beyond the bytes decoded.  A corrupted
+ * payload ends in a status or in wrong bytes inside its region.  Call-level
+ * checks and alignment as fsehip_compress_shared. */
+int fsehip_decompress_shared(uint32_t nstates, const uint8_t* d_table, const uint8_t* d_in,
+                             const fsehip_stream_desc* d_desc, uint32_t n_msgs, uint8_t* d_out,
+                             const uint32_t* d_raw_len, uint32_t* d_out_len, int32_t* d_status,
+                             fsehip_stream_t stream);
+
 /* The bitstream as device passes over `count` fields (a prefix scan of the
  * widths places every field; HBM-bound).
  *  fsehip_bitstack_write: fields LSB-first from bit 0 of d_out; d_out must
@@ -828,7 +931,8 @@ int fsehip_generate(int kind, double prob, uint64_t seed, uint32_t block_size, u
  * atomics, so every table checks its ranks and is rebuilt with lane-matching
  * ranks when the check fails.  counts[0..2] = the rebuilds so far on `device`
  * by the batch encoder, the decode-table builds and the building-block table
- * calls (0 on a correct GPU); reset != 0 zeroes them after reading.
+ * calls with the shared-table images (0 on a correct GPU); reset != 0 zeroes
+ * them after reading.
  * Synchronous. */
 int fsehip_rank_fallbacks(int device, uint32_t counts[3], int reset);
 
