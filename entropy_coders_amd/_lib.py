@@ -48,6 +48,9 @@ EXPORTS = (
     "fsehip_frame_decompress_ranges", "fsehip_frame_decompress_range",
     "norm_histogram_try_from", "fsehip_shared_table_bytes", "fsehip_shared_table_build", "fsehip_shared_out_bytes",
     "fsehip_compress_shared", "fsehip_decompress_shared",
+    "fsehip_planes_bound", "fsehip_planes_scratch_bytes", "fsehip_planes_read_header", "fsehip_planes_write_header",
+    "fsehip_planes_split", "fsehip_planes_merge", "fsehip_planes_compress", "fsehip_planes_decompress",
+    "fsehip_planes_ranges_scratch_bytes", "fsehip_planes_decompress_ranges",
 )
 
 STATUS = {
@@ -96,6 +99,17 @@ class FrameParams(C.Structure):
     """fsehip_frame_params: fsehip_params + chunk_blocks (0 = 4096)."""
     _fields_ = [("block_size", C.c_uint32), ("table_log", C.c_uint32), ("ckpt_interval", C.c_uint32),
                 ("max_table_log", C.c_uint32), ("nstates", C.c_uint32), ("chunk_blocks", C.c_uint32)]
+
+
+class PlanesInfo(C.Structure):
+    """fsehip_planes_info: a plane frame's header fields, stride = roundup(n_elems, 16)."""
+    _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
+                ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
+
+
+class PlanesRange(C.Structure):
+    """fsehip_planes_range: elements [elem_off, elem_off + n_elems) go to element dst_elem_off of d_out."""
+    _fields_ = [("elem_off", C.c_uint64), ("n_elems", C.c_uint64), ("dst_elem_off", C.c_uint64)]
 
 
 class Histogram(C.Structure):
@@ -208,6 +222,21 @@ def load() -> C.CDLL:
     lib.fsehip_frame_decompress_ranges.argtypes = [C.POINTER(FrameInfo), u32, P, u64, C.POINTER(FrameRange), u32, P, u64,
                                                    P, P, P]
     lib.fsehip_frame_decompress_range.argtypes = [C.POINTER(FrameInfo), u32, P, u64, u64, u64, P, u64, P, P]
+    PI, FI = C.POINTER(PlanesInfo), C.POINTER(FrameInfo)
+    lib.fsehip_planes_bound.argtypes = [u64, u32, u32]
+    lib.fsehip_planes_bound.restype = u64
+    lib.fsehip_planes_scratch_bytes.argtypes = [u64, u32]
+    lib.fsehip_planes_scratch_bytes.restype = u64
+    lib.fsehip_planes_read_header.argtypes = [P, sz, PI, FI]
+    lib.fsehip_planes_write_header.argtypes = [PI, P]
+    lib.fsehip_planes_split.argtypes = [u32, P, u64, P, P]
+    lib.fsehip_planes_merge.argtypes = [u32, P, u64, P, P]
+    lib.fsehip_planes_compress.argtypes = [C.POINTER(FrameParams), u32, P, u64, P, u64, P, u64, P, P, P]
+    lib.fsehip_planes_decompress.argtypes = [PI, FI, u32, P, u64, P, u64, P, u64, P, P, P]
+    lib.fsehip_planes_ranges_scratch_bytes.argtypes = [u32, C.POINTER(PlanesRange), u32]
+    lib.fsehip_planes_ranges_scratch_bytes.restype = u64
+    lib.fsehip_planes_decompress_ranges.argtypes = [PI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
+                                                    P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

@@ -788,6 +788,146 @@ int fsehip_frame_decompress_range(const fsehip_frame_info* info, uint32_t chunk_
                                   int32_t* d_result, fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * (2d) The plane frame: a byte-plane split for 2-, 4- and 8-byte elements
+ *
+ * bf16 / fp16 / fp32 tensors and int32 / int64 indices interleave one
+ * compressible byte per element (sign and exponent, the high bytes of small
+ * integers) with one to seven nearly random ones; one order-0 table per block
+ * averages them.  The plane frame puts byte k of every element into plane k
+ * and codes the planes with one unchanged frame of section 2b, whose encoder
+ * rule does the rest: exponent planes become FSE blocks, mantissa planes RAW
+ * blocks, the zero high planes of small integers RLE blocks.  This library's
+ * own container, version 1; integers little-endian, any byte address:
+ *
+ *    0  u8[4] magic "FSEP"
+ *    4  u8    version = 1
+ *    5  u8    elem_bytes w: 2, 4 or 8
+ *    6  u16   reserved = 0
+ *    8  u64   n_elems
+ *   16  one frame (section 2b) of the plane image, to the end of the buffer
+ *
+ * Plane image: with stride = roundup(n_elems, 16),
+ * image[k * stride + i] = raw[i * w + k] for k < w, i < n_elems (byte 0 is the
+ * element's lowest-addressed byte); the stride - n_elems pad bytes of each
+ * plane are zero, so plane frames are deterministic.  The inner frame's
+ * n_total must equal w * stride.  n_elems = 0 is valid: 16 + 32 bytes.  Planes
+ * share the inner frame, so at most w - 1 blocks straddle two planes.  The
+ * container stores the element width, not the dtype or the shape.
+ * ------------------------------------------------------------------------ */
+
+typedef struct {
+    uint32_t version, elem_bytes, reserved, pad_; /* pad_ is not stored */
+    uint64_t n_elems;
+    uint64_t stride; /* roundup(n_elems, 16): derived, not stored */
+} fsehip_planes_info;
+
+/* 16 + fsehip_frame_bound(w * stride, block_size): a capacity no plane frame
+ * of n_elems elements exceeds.  0 for elem_bytes outside {2, 4, 8} or when a
+ * size overflows 64 bits. */
+uint64_t fsehip_planes_bound(uint64_t n_elems, uint32_t elem_bytes, uint32_t block_size);
+/* w * stride, the plane image's bytes: the scratch of fsehip_planes_compress /
+ * fsehip_planes_decompress and the destination of fsehip_planes_split.  0 for
+ * a bad elem_bytes or on overflow (and for n_elems = 0). */
+uint64_t fsehip_planes_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes);
+/* Parse and validate the first 48 bytes of a plane frame (host pointer; len =
+ * bytes available): its own 16 into `out`, the inner frame's header into
+ * `inner`.  FSE_ERR_BAD_FRAME for len < 48, bad magic or version, elem_bytes
+ * outside {2, 4, 8}, a nonzero reserved field, w * stride overflowing, an
+ * inner header fsehip_frame_read_header rejects, or an inner n_total other
+ * than w * stride. */
+int fsehip_planes_read_header(const uint8_t* hdr, size_t len, fsehip_planes_info* out, fsehip_frame_info* inner);
+/* The 16 header bytes of `info` (stride and pad_ are not stored); BAD_ARG when
+ * the fields would not pass fsehip_planes_read_header. */
+int fsehip_planes_write_header(const fsehip_planes_info* info, uint8_t hdr[16]);
+
+/* The bare transforms, asynchronous on `stream`.
+ *  fsehip_planes_split: n_elems elements of elem_bytes at d_src -> the plane
+ *    image at d_dst (fsehip_planes_scratch_bytes, 16-byte aligned), pads
+ *    zeroed.  d_src need only be aligned to elem_bytes; reads of it go up to
+ *    roundup(n_elems * elem_bytes, 4) at most.
+ *  fsehip_planes_merge: the plane image at d_src (16-byte aligned) -> exactly
+ *    the n_elems * elem_bytes bytes at d_dst (16-byte aligned).
+ * BAD_ARG (a null or misaligned pointer with n_elems > 0), UNSUPPORTED
+ * (elem_bytes outside {2, 4, 8}; w * stride overflowing) and NO_DEVICE before
+ * any device use.  n_elems == 0 returns FSE_OK and does nothing. */
+int fsehip_planes_split(uint32_t elem_bytes, const void* d_src, uint64_t n_elems, uint8_t* d_dst,
+                        fsehip_stream_t stream);
+int fsehip_planes_merge(uint32_t elem_bytes, const uint8_t* d_src, uint64_t n_elems, void* d_dst,
+                        fsehip_stream_t stream);
+
+/* Compress n_elems elements of elem_bytes at d_src (aligned to elem_bytes)
+ * into one plane frame at d_out (any alignment; out_cap >= fsehip_planes_bound,
+ * else DST_TOO_SMALL): split into d_scratch (16-byte aligned, scratch_cap >=
+ * fsehip_planes_scratch_bytes, else DST_TOO_SMALL), fsehip_frame_compress of
+ * the image to d_out + 16, then the header and *d_out_len = 16 + the frame's
+ * length, written on the device in stream order.  d_result as in
+ * fsehip_frame_compress.  Only the first *d_out_len bytes of d_out are
+ * written.  The library allocates nothing for the planes (the frame call's
+ * workspace apart).  Call-level statuses as fsehip_frame_compress, with
+ * UNSUPPORTED also for elem_bytes outside {2, 4, 8}; all before any device
+ * use. */
+int fsehip_planes_compress(const fsehip_frame_params* p, uint32_t elem_bytes, const void* d_src, uint64_t n_elems,
+                           uint8_t* d_scratch, uint64_t scratch_cap, uint8_t* d_out, uint64_t out_cap,
+                           uint64_t* d_out_len, int32_t* d_result, fsehip_stream_t stream);
+
+/* Decompress the plane frame of in_len bytes at d_in (any alignment) whose
+ * first 48 bytes fsehip_planes_read_header parsed into `info` and `inner`:
+ * fsehip_frame_decompress of d_in + 16 into d_scratch (as above), then the
+ * merge into d_out (16-byte aligned; out_cap >= n_elems * elem_bytes, else
+ * DST_TOO_SMALL).  d_block_status (inner->n_blocks entries, may be NULL) and
+ * d_result are the frame call's.  The 16 header bytes on the device must equal
+ * `info`, and the frame check of fsehip_frame_decompress must pass: otherwise
+ * d_result[0] = BAD_FRAME, every block status BAD_FRAME, and no byte of d_out
+ * is touched.  A failed inner block leaves unspecified bytes in the elements
+ * that have a byte in it, and nowhere else.  BAD_ARG also for in_len < 48 and
+ * for an `info` / `inner` pair fsehip_planes_read_header would reject. */
+int fsehip_planes_decompress(const fsehip_planes_info* info, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                             const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap,
+                             void* d_out, uint64_t out_cap, int32_t* d_block_status, int32_t* d_result,
+                             fsehip_stream_t stream);
+
+/* One element range of a plane frame and where it goes (element units). */
+typedef struct {
+    uint64_t elem_off;     /* first element of the range */
+    uint64_t n_elems;      /* elements; 0 is valid */
+    uint64_t dst_elem_off; /* the range goes to d_out + dst_elem_off * elem_bytes */
+} fsehip_planes_range;
+
+/* The scratch fsehip_planes_decompress_ranges needs for a range list (host
+ * array): each range's w plane pieces, 16-byte aligned per range, then one
+ * int32 per plane piece.  0 for a bad elem_bytes or on overflow. */
+uint64_t fsehip_planes_ranges_scratch_bytes(uint32_t elem_bytes, const fsehip_planes_range* ranges,
+                                            uint32_t n_ranges);
+
+/* Decode element ranges of a plane frame without decoding the rest: range r
+ * becomes the w byte ranges k * stride + elem_off of the inner frame, all in
+ * one fsehip_frame_decompress_ranges call into d_scratch (16-byte aligned),
+ * so only the covered blocks are decoded; a pieces kernel then interleaves
+ * the plane pieces into d_out.  d_out may have any byte alignment.  Stores:
+ * exactly the n_elems * elem_bytes bytes of each range.  d_range_status
+ * (n_ranges entries, may be NULL): the status of the range's first failing
+ * plane range; d_result[0] = frame status, d_result[1] = element ranges with
+ * a failure.  On BAD_FRAME (the header on the device differs from `info`, or
+ * the inner frame check fails) every range status is BAD_FRAME and no byte of
+ * d_out is touched.  `ranges` is a host array, read before the call returns;
+ * the per-range parameters reach the device as kernel arguments, in stream
+ * order and with no host synchronisation of their own.
+ *
+ * Before any device use, in element units as fsehip_frame_decompress_ranges
+ * in bytes: BAD_ARG (a null pointer; in_len < 48; a bad info / inner pair;
+ * elem_off + n_elems overflowing or past info->n_elems; dst_elem_off +
+ * n_elems overflowing; overlapping destinations of non-empty ranges; a
+ * misaligned d_scratch), DST_TOO_SMALL ((dst_elem_off + n_elems) * elem_bytes
+ * > out_cap, or scratch_cap below fsehip_planes_ranges_scratch_bytes),
+ * UNSUPPORTED (more than 2^32 - 1 plane ranges), NO_DEVICE.  n_ranges == 0
+ * and empty ranges are valid. */
+int fsehip_planes_decompress_ranges(const fsehip_planes_info* info, const fsehip_frame_info* inner,
+                                    uint32_t chunk_blocks, const uint8_t* d_in, uint64_t in_len,
+                                    const fsehip_planes_range* ranges, uint32_t n_ranges, uint8_t* d_scratch,
+                                    uint64_t scratch_cap, void* d_out, uint64_t out_cap, int32_t* d_range_status,
+                                    int32_t* d_result, fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
  *
  * The crate's `pub mod fse` lets a caller code any number of messages against
