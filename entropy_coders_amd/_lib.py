@@ -51,6 +51,9 @@ EXPORTS = (
     "fsehip_planes_bound", "fsehip_planes_scratch_bytes", "fsehip_planes_read_header", "fsehip_planes_write_header",
     "fsehip_planes_split", "fsehip_planes_merge", "fsehip_planes_compress", "fsehip_planes_decompress",
     "fsehip_planes_ranges_scratch_bytes", "fsehip_planes_decompress_ranges",
+    "fsehip_delta_bound", "fsehip_delta_scratch_bytes", "fsehip_delta_read_header", "fsehip_delta_write_header",
+    "fsehip_delta_encode", "fsehip_delta_decode", "fsehip_delta_compress", "fsehip_delta_decompress",
+    "fsehip_delta_ranges_scratch_bytes", "fsehip_delta_decompress_ranges",
 )
 
 STATUS = {
@@ -110,6 +113,15 @@ class PlanesInfo(C.Structure):
 class PlanesRange(C.Structure):
     """fsehip_planes_range: elements [elem_off, elem_off + n_elems) go to element dst_elem_off of d_out."""
     _fields_ = [("elem_off", C.c_uint64), ("n_elems", C.c_uint64), ("dst_elem_off", C.c_uint64)]
+
+
+DELTA_RESTART = 4096  # FSEHIP_DELTA_RESTART: elements between the delta frame's restarts
+
+
+class DeltaInfo(C.Structure):
+    """fsehip_delta_info: a delta frame's header fields, stride = roundup(n_elems, 16)."""
+    _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
+                ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
 
 
 class Histogram(C.Structure):
@@ -237,6 +249,21 @@ def load() -> C.CDLL:
     lib.fsehip_planes_ranges_scratch_bytes.restype = u64
     lib.fsehip_planes_decompress_ranges.argtypes = [PI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
                                                     P, P, P]
+    DI = C.POINTER(DeltaInfo)
+    lib.fsehip_delta_bound.argtypes = [u64, u32, u32]
+    lib.fsehip_delta_bound.restype = u64
+    lib.fsehip_delta_scratch_bytes.argtypes = [u64, u32]
+    lib.fsehip_delta_scratch_bytes.restype = u64
+    lib.fsehip_delta_read_header.argtypes = [P, sz, DI, FI]
+    lib.fsehip_delta_write_header.argtypes = [DI, P]
+    lib.fsehip_delta_encode.argtypes = [u32, P, u64, P, P]
+    lib.fsehip_delta_decode.argtypes = [u32, P, u64, P, P]
+    lib.fsehip_delta_compress.argtypes = [C.POINTER(FrameParams), u32, P, u64, P, u64, P, u64, P, P, P]
+    lib.fsehip_delta_decompress.argtypes = [DI, FI, u32, P, u64, P, u64, P, u64, P, P, P]
+    lib.fsehip_delta_ranges_scratch_bytes.argtypes = [u32, C.POINTER(PlanesRange), u32]
+    lib.fsehip_delta_ranges_scratch_bytes.restype = u64
+    lib.fsehip_delta_decompress_ranges.argtypes = [DI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
+                                                   P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

@@ -6,9 +6,37 @@
 #pragma once
 #include <stdint.h>
 
+#include <algorithm>
+#include <utility>
+#include <vector>
+
 #include "../../include/fsehip.h"
 
 namespace fsehip {
+
+// The range rules the element-range calls share (fsehip_planes_decompress_ranges,
+// fsehip_delta_decompress_ranges) for a tensor of n_elems elements of w bytes
+// and a destination of out_cap bytes: BAD_ARG, DST_TOO_SMALL or FSE_OK.
+// Inline, so that each host-only translation unit builds on its own.
+inline int check_elem_ranges(uint64_t n_elems, uint64_t w, uint64_t out_cap, const fsehip_planes_range* ranges,
+                             uint32_t n_ranges) {
+    if (n_ranges && !ranges) return FSE_ERR_BAD_ARG;
+    std::vector<std::pair<uint64_t, uint64_t>> dst;  // non-empty destinations [lo, hi), in elements
+    dst.reserve(n_ranges);
+    uint64_t dst_end = 0;
+    for (uint32_t r = 0; r < n_ranges; ++r) {
+        const fsehip_planes_range& g = ranges[r];
+        if (g.elem_off + g.n_elems < g.elem_off || g.elem_off + g.n_elems > n_elems) return FSE_ERR_BAD_ARG;
+        if (g.dst_elem_off + g.n_elems < g.dst_elem_off) return FSE_ERR_BAD_ARG;
+        if (g.n_elems) dst.emplace_back(g.dst_elem_off, g.dst_elem_off + g.n_elems);
+        dst_end = std::max(dst_end, g.dst_elem_off + g.n_elems);
+    }
+    if (!std::is_sorted(dst.begin(), dst.end())) std::sort(dst.begin(), dst.end());
+    for (size_t i = 1; i < dst.size(); ++i)
+        if (dst[i].first < dst[i - 1].second) return FSE_ERR_BAD_ARG;
+    if (dst_end > out_cap / w) return FSE_ERR_DST_TOO_SMALL;  // an empty range's place counts too
+    return FSE_OK;
+}
 
 // FSE_OK when `info` and `inner` are a pair fsehip_planes_read_header gives
 // (each valid, inner->n_total = w * stride), BAD_ARG otherwise.

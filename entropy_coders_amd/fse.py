@@ -11,8 +11,8 @@ import threading
 
 import numpy as np
 
-from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, EncodeTable, FrameInfo,
-                   FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check,
+from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, DeltaInfo, EncodeTable,
+                   FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check,
                    load)
 
 
@@ -852,10 +852,10 @@ class BlockCodec:
               "fsehip_planes_read_header")
         return info, inner
 
-    def _check_dtype(self, info: PlanesInfo, dtype) -> None:
+    def _check_dtype(self, info, dtype, kind: str = "plane") -> None:
         w = self.torch.empty(0, dtype=dtype).element_size()
         if w != info.elem_bytes:
-            raise ValueError(f"dtype {dtype} has {w}-byte elements, the plane frame holds {info.elem_bytes}-byte ones")
+            raise ValueError(f"dtype {dtype} has {w}-byte elements, the {kind} frame holds {info.elem_bytes}-byte ones")
 
     def decompress_planes_into(self, buf, info: PlanesInfo, inner: FrameInfo, scratch, out, block_status, result,
                                chunk_blocks: int = 0) -> None:
@@ -945,6 +945,164 @@ class BlockCodec:
         check(int(status[0].item()), "plane frame range")
         return views[0]
 
+    # ------------------------------------------------------------ the delta frame
+    # fsehip.h section 2e: zigzag differences of neighbouring elements with a
+    # restart every 4,096, split into byte planes and coded by one frame.  For
+    # integer tensors that grow (sorted ids, offsets, timestamps); any dtype
+    # of 1, 2, 4 or 8 bytes round-trips, floats gain nothing.
+    @staticmethod
+    def _delta_elem_bytes(x) -> int:
+        w = x.element_size()
+        if w not in (1, 2, 4, 8):
+            raise ValueError(f"element size {w}: the delta frame takes 1, 2, 4 or 8 bytes")
+        if not x.is_contiguous():
+            raise ValueError("compress_delta needs a contiguous tensor")
+        return w
+
+    def delta_bound(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_delta_bound`: a capacity no delta frame of n_elems elements exceeds."""
+        return int(self.lib.fsehip_delta_bound(n_elems, elem_bytes, self.block_size))
+
+    def delta_scratch_bytes(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_delta_scratch_bytes`: the delta image's bytes."""
+        return int(self.lib.fsehip_delta_scratch_bytes(n_elems, elem_bytes))
+
+    def delta_encode(self, x):
+        """`fsehip_delta_encode`: the delta image of a contiguous device tensor (uint8, pads zeroed)."""
+        w = self._delta_elem_bytes(x)
+        image = self.torch.empty(self.delta_scratch_bytes(x.numel(), w), dtype=self.torch.uint8, device=self.device)
+        check(self.lib.fsehip_delta_encode(w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(image.data_ptr()),
+                                           self._stream()), "fsehip_delta_encode")
+        return image
+
+    def delta_decode(self, image, n_elems: int, dtype):
+        """`fsehip_delta_decode`: n_elems elements of `dtype` from a delta image."""
+        out = self.torch.empty(n_elems, dtype=dtype, device=self.device)
+        check(self.lib.fsehip_delta_decode(out.element_size(), C.c_void_p(image.data_ptr()), n_elems,
+                                           C.c_void_p(out.data_ptr()), self._stream()), "fsehip_delta_decode")
+        return out
+
+    def compress_delta_into(self, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_delta_compress`, no synchronisation: `scratch` a uint8
+        device tensor of >= delta_scratch_bytes, `out` of >= delta_bound
+        bytes (any alignment), `out_len` one int64, `result` two int32."""
+        w = self._delta_elem_bytes(x)
+        p = FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
+                        chunk_blocks)
+        check(self.lib.fsehip_delta_compress(
+            C.byref(p), w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+            C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()),
+            self._stream()), "fsehip_delta_compress")
+
+    def compress_delta(self, x, chunk_blocks: int = 0):
+        """Compress a contiguous device tensor of 1-, 2-, 4- or 8-byte
+        elements into one delta frame: a uint8 device tensor of its exact
+        length.  One synchronisation, to read the length."""
+        t = self.torch
+        w = self._delta_elem_bytes(x)
+        scratch = t.empty(self.delta_scratch_bytes(x.numel(), w), dtype=t.uint8, device=self.device)
+        out = t.empty(self.delta_bound(x.numel(), w), dtype=t.uint8, device=self.device)
+        out_len = t.zeros(1, dtype=t.int64, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.compress_delta_into(x, scratch, out, out_len, result, chunk_blocks)
+        return out[: int(out_len.item())]
+
+    @staticmethod
+    def delta_info(buf):
+        """`fsehip_delta_read_header` of a delta frame given as bytes, a numpy
+        array or a tensor (its first 48 bytes come to the host): (DeltaInfo,
+        the inner frame's FrameInfo); raises FseError (BAD_FRAME) otherwise."""
+        if hasattr(buf, "data_ptr"):  # a torch tensor
+            head = buf[:48].cpu().numpy().tobytes()
+        else:
+            head = bytes(memoryview(buf)[:48])
+        a = np.frombuffer(head, dtype=np.uint8)
+        info, inner = DeltaInfo(), FrameInfo()
+        check(load().fsehip_delta_read_header(_p(a), len(a), C.byref(info), C.byref(inner)),
+              "fsehip_delta_read_header")
+        return info, inner
+
+    def decompress_delta_into(self, buf, info: DeltaInfo, inner: FrameInfo, scratch, out, block_status, result,
+                              chunk_blocks: int = 0) -> None:
+        """`fsehip_delta_decompress`, no synchronisation: `scratch` >=
+        inner.n_total bytes, `out` info.n_elems elements (16-byte aligned),
+        `block_status` inner.n_blocks int32 or None, `result` two int32."""
+        check(self.lib.fsehip_delta_decompress(
+            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
+            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
+            out.numel() * out.element_size(),
+            C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_delta_decompress")
+
+    def decompress_delta(self, buf, dtype, chunk_blocks: int = 0):
+        """Decode a delta frame (a uint8 device tensor) into a 1-D tensor of
+        `dtype`, whose size must be the frame's element width (ValueError
+        otherwise).  Returns (out, block_status); raises FseError for a
+        frame-level error (BAD_FRAME)."""
+        t = self.torch
+        info, inner = self.delta_info(buf)
+        self._check_dtype(info, dtype, "delta")
+        scratch = t.empty(inner.n_total, dtype=t.uint8, device=self.device)
+        out = t.empty(info.n_elems, dtype=dtype, device=self.device)
+        status = t.zeros(inner.n_blocks, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_delta_into(buf, info, inner, scratch, out, status, result, chunk_blocks)
+        check(int(result[0].item()), "delta frame")
+        return out, status
+
+    def delta_ranges_scratch_bytes(self, elem_bytes: int, ranges) -> int:
+        """`fsehip_delta_ranges_scratch_bytes` for a sequence of triples or a `planes_ranges` array."""
+        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        return int(self.lib.fsehip_delta_ranges_scratch_bytes(elem_bytes, arr, n))
+
+    def decompress_delta_ranges_into(self, buf, info: DeltaInfo, inner: FrameInfo, ranges, scratch, out,
+                                     range_status, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_delta_decompress_ranges`, no synchronisation: `ranges` a
+        sequence of (elem_off, n_elems, dst_elem_off) or what `planes_ranges`
+        made of one; `scratch` >= delta_ranges_scratch_bytes; range r goes
+        to out[dst_elem_off: dst_elem_off + n_elems] (`out` of the frame's
+        element width, any alignment)."""
+        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        check(self.lib.fsehip_delta_decompress_ranges(
+            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(), arr, n,
+            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
+            out.numel() * out.element_size(),
+            C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_delta_decompress_ranges")
+
+    def decompress_delta_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0):
+        """Decode the element ranges [(elem_off, count), ...] of a delta frame
+        without decoding the rest (each from its restart group's first
+        element on).  The ranges are packed back to back into one tensor of
+        `dtype`; returns (list of views of it, one per range, and the int32
+        range statuses).  Raises FseError for a frame-level error."""
+        t = self.torch
+        info, inner = self.delta_info(buf)
+        self._check_dtype(info, dtype, "delta")
+        packed, at = [], 0
+        for s, n in ranges:
+            packed.append((s, n, at))
+            at += n
+        arr = self.planes_ranges(packed)
+        scratch = t.empty(max(self.delta_ranges_scratch_bytes(info.elem_bytes, arr), 16), dtype=t.uint8,
+                          device=self.device)
+        out = t.empty(at, dtype=dtype, device=self.device)
+        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_delta_ranges_into(buf, info, inner, arr, scratch, out, status, result, chunk_blocks)
+        check(int(result[0].item()), "delta frame")
+        return [out[d: d + n] for _, n, d in packed], status
+
+    def decompress_delta_range(self, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0):
+        """Elements [elem_off, elem_off + count) of a delta frame as a tensor
+        of `dtype`; raises FseError for a frame-level error or with the
+        status of the first failed block the range needs."""
+        views, status = self.decompress_delta_ranges(buf, dtype, [(elem_off, count)], chunk_blocks)
+        check(int(status[0].item()), "delta frame range")
+        return views[0]
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -1028,6 +1186,46 @@ def planes_decompress(data, dtype, device=None) -> np.ndarray:
     if st.any():
         b = int(np.flatnonzero(st)[0])
         raise FseError(int(st[b]), f"plane frame block {b}")
+    return out.cpu().numpy().view(dt)
+
+
+# the integer view a host array of each item size travels as
+_INT_VIEW = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}
+
+
+def delta_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
+                   device=None) -> bytes:
+    """Compress a numpy array of item size 1, 2, 4 or 8 into one delta frame
+    (fsehip.h section 2e) on the GPU; copies through torch.  The element width
+    is stored, the dtype and the shape are not."""
+    import torch
+
+    a = np.ascontiguousarray(data)
+    if a.dtype.itemsize not in _INT_VIEW:
+        raise ValueError(f"item size {a.dtype.itemsize}: the delta frame takes 1, 2, 4 or 8 bytes")
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    src = torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device)
+    return codec.compress_delta(src).cpu().numpy().tobytes()
+
+
+def delta_decompress(data, dtype, device=None) -> np.ndarray:
+    """Decode a delta frame held in host memory into a 1-D numpy array of
+    `dtype` (its item size must be the frame's element width); raises FseError
+    on a frame-level error or with the first failed block's status."""
+    import torch
+
+    dt = np.dtype(dtype)
+    codec = BlockCodec(device=device)
+    info, _ = BlockCodec.delta_info(_buf(data))  # not a delta frame: BAD_FRAME before any device work
+    if dt.itemsize != info.elem_bytes:
+        raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the delta frame holds {info.elem_bytes}-byte ones")
+    buf = torch.from_numpy(_buf(data).copy()).to(codec.device)
+    out, status = codec.decompress_delta(buf, getattr(torch, np.dtype(_INT_VIEW[info.elem_bytes]).name))
+    st = status.cpu().numpy()
+    if st.any():
+        b = int(np.flatnonzero(st)[0])
+        raise FseError(int(st[b]), f"delta frame block {b}")
     return out.cpu().numpy().view(dt)
 
 
@@ -1177,4 +1375,4 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "encode_table_new", "frame_compress", "frame_decompress", "frame_decompress_range",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal", "SharedTable", "norm_histogram_try_from",
-           "planes_compress", "planes_decompress"]
+           "planes_compress", "planes_decompress", "delta_compress", "delta_decompress"]

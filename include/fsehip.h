@@ -928,6 +928,129 @@ int fsehip_planes_decompress_ranges(const fsehip_planes_info* info, const fsehip
                                     int32_t* d_result, fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * (2e) The delta frame: element delta with restarts for integer tensors
+ *
+ * Index tensors that grow -- sorted ids, CSR and embedding-bag offsets,
+ * timestamps, sampled signals -- keep most of their bytes live under the
+ * plane split of section 2d, because the values grow; their differences are
+ * small.  The delta frame codes the zigzag differences of neighbouring
+ * elements, split into byte planes, with one unchanged frame of section 2b.
+ * This library's own container, version 1; integers little-endian, any byte
+ * address:
+ *
+ *    0  u8[4] magic "FSED"
+ *    4  u8    version = 1
+ *    5  u8    elem_bytes w: 1, 2, 4 or 8
+ *    6  u16   reserved = 0
+ *    8  u64   n_elems
+ *   16  one frame (section 2b) of the delta image, to the end of the buffer
+ *
+ * Delta image: the elements are read as unsigned little-endian integers x_i
+ * of w bytes, whatever the dtype, and all arithmetic is mod 2^(8 w).
+ *   d_i = x_i                 when i % FSEHIP_DELTA_RESTART == 0,
+ *         x_i - x_(i-1)       otherwise;
+ *   z_i = (d_i << 1) ^ (0 - (d_i >> (8 w - 1)))            (zigzag);
+ *   image[k * stride + i] = byte k of z_i, k < w, i < n_elems,
+ * with stride = roundup(n_elems, 16) and the stride - n_elems pad bytes of
+ * each plane zero: for w = 2, 4, 8 the plane image (section 2d) of z, for
+ * w = 1 z itself, padded.  The inner frame's n_total must equal w * stride.
+ * Decode: d_i = (z_i >> 1) ^ (0 - (z_i & 1)), and x_i = the sum of d from the
+ * first element of i's restart group through i.  The restart interval is a
+ * constant of version 1, not a header field: an element range needs only its
+ * own restart groups (4096 bytes per plane each), so byte-range decode of the
+ * inner frame keeps working, and no sum ever crosses a group.  n_elems = 0 is
+ * valid: 16 + 32 bytes.  The container stores the element width, not the
+ * dtype or the shape.  The filter is for integers; floats gain nothing
+ * (DESIGN.md section 5 "Delta").
+ * ------------------------------------------------------------------------ */
+
+#define FSEHIP_DELTA_RESTART 4096u /* elements between restarts, version 1 */
+
+typedef struct {
+    uint32_t version, elem_bytes, reserved, pad_; /* pad_ is not stored */
+    uint64_t n_elems;
+    uint64_t stride; /* roundup(n_elems, 16): derived, not stored */
+} fsehip_delta_info;
+
+/* 16 + fsehip_frame_bound(w * stride, block_size): a capacity no delta frame
+ * of n_elems elements exceeds.  0 for elem_bytes outside {1, 2, 4, 8} or when
+ * a size overflows 64 bits. */
+uint64_t fsehip_delta_bound(uint64_t n_elems, uint32_t elem_bytes, uint32_t block_size);
+/* w * stride, the delta image's bytes: the scratch of fsehip_delta_compress /
+ * fsehip_delta_decompress and the destination of fsehip_delta_encode.  0 for
+ * a bad elem_bytes or on overflow (and for n_elems = 0). */
+uint64_t fsehip_delta_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes);
+/* Parse and validate the first 48 bytes of a delta frame (host pointer; len =
+ * bytes available), as fsehip_planes_read_header: BAD_FRAME for len < 48, bad
+ * magic or version, elem_bytes outside {1, 2, 4, 8}, a nonzero reserved
+ * field, w * stride overflowing, an inner header fsehip_frame_read_header
+ * rejects, or an inner n_total other than w * stride.  Outputs are zeroed on
+ * every reject. */
+int fsehip_delta_read_header(const uint8_t* hdr, size_t len, fsehip_delta_info* out, fsehip_frame_info* inner);
+/* The 16 header bytes of `info` (stride and pad_ are not stored); BAD_ARG when
+ * the fields would not pass fsehip_delta_read_header. */
+int fsehip_delta_write_header(const fsehip_delta_info* info, uint8_t hdr[16]);
+
+/* The bare transforms, asynchronous on `stream`.
+ *  fsehip_delta_encode: n_elems elements of elem_bytes at d_src -> the delta
+ *    image at d_dst (fsehip_delta_scratch_bytes, 16-byte aligned), pads
+ *    zeroed.  d_src need only be aligned to elem_bytes; reads of it go up to
+ *    roundup(n_elems * elem_bytes, 4) at most.
+ *  fsehip_delta_decode: the delta image at d_src (16-byte aligned) -> exactly
+ *    the n_elems * elem_bytes bytes at d_dst (16-byte aligned).
+ * BAD_ARG (a null or misaligned pointer with n_elems > 0), UNSUPPORTED
+ * (elem_bytes outside {1, 2, 4, 8}; w * stride overflowing) and NO_DEVICE
+ * before any device use.  n_elems == 0 returns FSE_OK and does nothing. */
+int fsehip_delta_encode(uint32_t elem_bytes, const void* d_src, uint64_t n_elems, uint8_t* d_dst,
+                        fsehip_stream_t stream);
+int fsehip_delta_decode(uint32_t elem_bytes, const uint8_t* d_src, uint64_t n_elems, void* d_dst,
+                        fsehip_stream_t stream);
+
+/* fsehip_planes_compress with the delta image in place of the plane image:
+ * the same arguments, alignment rules (d_src to elem_bytes, d_scratch to 16,
+ * d_out any), capacities (fsehip_delta_scratch_bytes, fsehip_delta_bound) and
+ * statuses, UNSUPPORTED for elem_bytes outside {1, 2, 4, 8}; nothing
+ * allocated for the transform, no host synchronisation. */
+int fsehip_delta_compress(const fsehip_frame_params* p, uint32_t elem_bytes, const void* d_src, uint64_t n_elems,
+                          uint8_t* d_scratch, uint64_t scratch_cap, uint8_t* d_out, uint64_t out_cap,
+                          uint64_t* d_out_len, int32_t* d_result, fsehip_stream_t stream);
+
+/* fsehip_planes_decompress for a delta frame whose first 48 bytes
+ * fsehip_delta_read_header parsed into `info` and `inner`: the same
+ * arguments, rules and statuses (d_out 16-byte aligned); on BAD_FRAME every
+ * block status is BAD_FRAME and no byte of d_out is touched.  A failed inner
+ * block costs the elements from the first one with a byte in it to the end of
+ * their restart groups (their sums run through it); every other element is
+ * exact. */
+int fsehip_delta_decompress(const fsehip_delta_info* info, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                            const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap,
+                            void* d_out, uint64_t out_cap, int32_t* d_block_status, int32_t* d_result,
+                            fsehip_stream_t stream);
+
+/* The scratch fsehip_delta_decompress_ranges needs for a range list (host
+ * array).  A range is decoded from e0 = elem_off rounded down to a multiple
+ * of FSEHIP_DELTA_RESTART: per range w plane pieces of
+ * roundup(elem_off + n_elems - e0, 16) bytes, then one int32 per plane piece,
+ * rounded up to 16.  0 for a bad elem_bytes or on overflow. */
+uint64_t fsehip_delta_ranges_scratch_bytes(uint32_t elem_bytes, const fsehip_planes_range* ranges,
+                                           uint32_t n_ranges);
+
+/* fsehip_planes_decompress_ranges for a delta frame: each non-empty range
+ * becomes the w byte ranges k * stride + e0 .. k * stride + elem_off + n_elems
+ * of the inner frame, one fsehip_frame_decompress_ranges call into d_scratch
+ * decodes only the blocks they cover, and a pieces kernel sums each restart
+ * group and stores exactly the n_elems * elem_bytes bytes of each range at
+ * d_out + dst_elem_off * elem_bytes (any byte alignment).  The range rules,
+ * statuses (d_range_status, d_result) and argument checks are those of
+ * fsehip_planes_decompress_ranges, with fsehip_delta_ranges_scratch_bytes for
+ * the scratch.  A range's status covers the blocks from e0 on. */
+int fsehip_delta_decompress_ranges(const fsehip_delta_info* info, const fsehip_frame_info* inner,
+                                   uint32_t chunk_blocks, const uint8_t* d_in, uint64_t in_len,
+                                   const fsehip_planes_range* ranges, uint32_t n_ranges, uint8_t* d_scratch,
+                                   uint64_t scratch_cap, void* d_out, uint64_t out_cap, int32_t* d_range_status,
+                                   int32_t* d_result, fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
  *
  * The crate's `pub mod fse` lets a caller code any number of messages against
