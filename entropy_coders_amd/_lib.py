@@ -54,6 +54,9 @@ EXPORTS = (
     "fsehip_delta_bound", "fsehip_delta_scratch_bytes", "fsehip_delta_read_header", "fsehip_delta_write_header",
     "fsehip_delta_encode", "fsehip_delta_decode", "fsehip_delta_compress", "fsehip_delta_decompress",
     "fsehip_delta_ranges_scratch_bytes", "fsehip_delta_decompress_ranges",
+    "fsehip_crc32", "fsehip_crc32_combine", "fsehip_check_bytes", "fsehip_check_read_header",
+    "fsehip_check_write_header", "fsehip_sealed_read_header", "fsehip_check_build", "fsehip_check_verify",
+    "fsehip_check_ranges_verified_bytes", "fsehip_check_verify_ranges",
 )
 
 STATUS = {
@@ -61,7 +64,7 @@ STATUS = {
     -5: "BAD_HEADER", -6: "NO_MARKER", -7: "DST_TOO_SMALL", -8: "TABLELOG_RANGE",
     -9: "CURSED", -10: "BAD_TABLE", -11: "BAD_ARG", -12: "HIP", -13: "LENGTH_MISMATCH",
     -14: "UNSUPPORTED", -15: "NO_DEVICE", -16: "BAD_SIDECAR", -17: "ENCODER_INIT",
-    -18: "EOF", -19: "BAD_FRAME", -20: "SYMBOL_NOT_IN_TABLE",
+    -18: "EOF", -19: "BAD_FRAME", -20: "SYMBOL_NOT_IN_TABLE", -21: "CHECKSUM",
 }
 
 
@@ -122,6 +125,17 @@ class DeltaInfo(C.Structure):
     """fsehip_delta_info: a delta frame's header fields, stride = roundup(n_elems, 16)."""
     _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
                 ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
+
+
+CHECK_CRC32 = 1  # FSEHIP_CHECK_CRC32: the check record's algorithm
+SEALED_KINDS = ("frame", "planes", "delta")  # FSEHIP_SEALED_FRAME / _PLANES / _DELTA
+
+
+class CheckInfo(C.Structure):
+    """fsehip_check_info: a check record's header fields; the table follows at byte 32."""
+    _fields_ = [("version", C.c_uint32), ("algorithm", C.c_uint32), ("check_log", C.c_uint32), ("reserved", C.c_uint32),
+                ("n_content", C.c_uint64), ("n_cb", C.c_uint32), ("content_crc", C.c_uint32),
+                ("header_crc", C.c_uint32), ("pad_", C.c_uint32)]
 
 
 class Histogram(C.Structure):
@@ -264,6 +278,20 @@ def load() -> C.CDLL:
     lib.fsehip_delta_ranges_scratch_bytes.restype = u64
     lib.fsehip_delta_decompress_ranges.argtypes = [DI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
                                                    P, P, P]
+    CI = C.POINTER(CheckInfo)
+    lib.fsehip_crc32.argtypes = [u32, P, sz]
+    lib.fsehip_crc32.restype = u32
+    lib.fsehip_crc32_combine.argtypes = [u32, u32, u64]
+    lib.fsehip_crc32_combine.restype = u32
+    lib.fsehip_check_bytes.argtypes = [u64, u32]
+    lib.fsehip_check_bytes.restype = u64
+    lib.fsehip_check_read_header.argtypes = [P, sz, CI]
+    lib.fsehip_check_write_header.argtypes = [CI, P]
+    lib.fsehip_sealed_read_header.argtypes = [P, sz, CI, C.POINTER(u32), C.POINTER(u64)]
+    lib.fsehip_check_build.argtypes = [u32, P, u64, P, P]
+    lib.fsehip_check_verify.argtypes = [CI, P, P, u64, P, P, P]
+    lib.fsehip_check_ranges_verified_bytes.argtypes = [CI, C.POINTER(FrameRange), u32, C.POINTER(u64)]
+    lib.fsehip_check_verify_ranges.argtypes = [CI, P, C.POINTER(FrameRange), u32, P, u64, P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

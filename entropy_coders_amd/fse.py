@@ -11,9 +11,9 @@ import threading
 
 import numpy as np
 
-from ._lib import (BitStackReaderState, BitStackWriterState, BitStreamReaderState, DecodeTable, DeltaInfo, EncodeTable,
-                   FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check,
-                   load)
+from ._lib import (SEALED_KINDS, BitStackReaderState, BitStackWriterState, BitStreamReaderState, CheckInfo, DecodeTable,
+                   DeltaInfo, EncodeTable, FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params,
+                   PlanesInfo, PlanesRange, check, load)
 
 
 def _buf(data) -> np.ndarray:
@@ -1103,6 +1103,285 @@ class BlockCodec:
         check(int(status[0].item()), "delta frame range")
         return views[0]
 
+    # ------------------------------------------------------------ the check record and sealed buffers
+    # fsehip.h section 2f: a CRC-32 (zlib's) per check block of the content,
+    # in a record of its own in front of an unchanged container.
+    @staticmethod
+    def _check_log(check_block: int) -> int:
+        log = int(check_block).bit_length() - 1
+        if check_block != 1 << log or not 8 <= log <= 16:
+            raise ValueError(f"check_block {check_block}: a power of two from 256 to 65536")
+        return log
+
+    @staticmethod
+    def _content_bytes(x) -> int:
+        if not x.is_contiguous():
+            raise ValueError("the check record needs a contiguous tensor")
+        return x.numel() * x.element_size()
+
+    def check_bytes(self, n_content: int, check_block: int = 65536) -> int:
+        """`fsehip_check_bytes`: the record's size for n_content bytes."""
+        return int(self.lib.fsehip_check_bytes(n_content, self._check_log(check_block)))
+
+    def check_build_into(self, x, record, check_block: int = 65536) -> None:
+        """`fsehip_check_build`, no synchronisation: the record of the bytes of
+        `x` (any contiguous tensor, any alignment) into `record`, a uint8
+        device tensor of check_bytes (any alignment)."""
+        n = self._content_bytes(x)
+        if record.numel() < self.check_bytes(n, check_block):
+            raise FseError(-7, "fsehip_check_build")
+        check(self.lib.fsehip_check_build(self._check_log(check_block), C.c_void_p(x.data_ptr()), n,
+                                          C.c_void_p(record.data_ptr()), self._stream()), "fsehip_check_build")
+
+    def check_build(self, x, check_block: int = 65536):
+        """The check record of a contiguous device tensor's bytes: a uint8 device tensor."""
+        record = self.torch.empty(self.check_bytes(self._content_bytes(x), check_block), dtype=self.torch.uint8,
+                                  device=self.device)
+        self.check_build_into(x, record, check_block)
+        return record
+
+    @staticmethod
+    def check_info(record) -> CheckInfo:
+        """`fsehip_check_read_header` of a record given as bytes, a numpy array
+        or a tensor (its first 32 bytes come to the host); raises FseError
+        (BAD_FRAME) for anything that is not a check record's header."""
+        if hasattr(record, "data_ptr"):  # a torch tensor
+            head = record[:32].cpu().numpy().tobytes()
+        else:
+            head = bytes(memoryview(record)[:32])
+        a = np.frombuffer(head, dtype=np.uint8)
+        info = CheckInfo()
+        check(load().fsehip_check_read_header(_p(a), len(a), C.byref(info)), "fsehip_check_read_header")
+        return info
+
+    def check_verify_into(self, record, info: CheckInfo, x, check_status, result) -> None:
+        """`fsehip_check_verify`, no synchronisation: `check_status` info.n_cb
+        int32, `result` two int32 (OK / CHECKSUM of the whole content / BAD_FRAME,
+        failed check blocks)."""
+        check(self.lib.fsehip_check_verify(
+            C.byref(info), C.c_void_p(record.data_ptr()), C.c_void_p(x.data_ptr()), self._content_bytes(x),
+            C.c_void_p(check_status.data_ptr()), C.c_void_p(result.data_ptr()), self._stream()), "fsehip_check_verify")
+
+    def check_verify(self, record, x):
+        """Compare a record (a uint8 device tensor) with the bytes of `x`:
+        (check_status, result), both int32 device tensors."""
+        t = self.torch
+        info = self.check_info(record)
+        status = t.zeros(info.n_cb, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.check_verify_into(record, info, x, status, result)
+        return status, result
+
+    def check_ranges_verified_bytes(self, info: CheckInfo, ranges) -> int:
+        """`fsehip_check_ranges_verified_bytes`: the bytes of the byte ranges
+        (src_off, len, dst_off) that lie in wholly covered check blocks."""
+        arr = ranges if isinstance(ranges, C.Array) else self.frame_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        out = C.c_uint64(0)
+        check(self.lib.fsehip_check_ranges_verified_bytes(C.byref(info), arr, n, C.byref(out)),
+              "fsehip_check_ranges_verified_bytes")
+        return int(out.value)
+
+    def check_verify_ranges_into(self, record, info: CheckInfo, ranges, out, range_status, result) -> None:
+        """`fsehip_check_verify_ranges`, no synchronisation: `ranges` byte
+        triples (src_off, len, dst_off) or a `frame_ranges` array, range r's
+        bytes at byte dst_off of `out` (any tensor, any alignment);
+        `range_status` len(ranges) int32, `result` two int32."""
+        arr = ranges if isinstance(ranges, C.Array) else self.frame_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        check(self.lib.fsehip_check_verify_ranges(
+            C.byref(info), C.c_void_p(record.data_ptr()), arr, n, C.c_void_p(out.data_ptr()),
+            out.numel() * out.element_size(), C.c_void_p(range_status.data_ptr()), C.c_void_p(result.data_ptr()),
+            self._stream()), "fsehip_check_verify_ranges")
+
+    def _sealed_kind(self, x, kind: str) -> int:
+        if kind == "frame":
+            if x.element_size() != 1:
+                raise ValueError("a sealed frame takes a 1-byte tensor; wider elements go to kind='planes' or 'delta'")
+            return 1
+        if kind == "planes":
+            return self._elem_bytes(x)
+        if kind == "delta":
+            return self._delta_elem_bytes(x)
+        raise ValueError(f"kind {kind!r}: 'frame', 'planes' or 'delta'")
+
+    def sealed_bound(self, x, kind: str = "frame", check_block: int = 65536) -> int:
+        """A capacity no sealed buffer of `x` exceeds: the record, then the container's bound."""
+        w = self._sealed_kind(x, kind)
+        inner = {"frame": lambda: self.frame_bound(x.numel()), "planes": lambda: self.planes_bound(x.numel(), w),
+                 "delta": lambda: self.delta_bound(x.numel(), w)}[kind]()
+        return self.check_bytes(self._content_bytes(x), check_block) + inner
+
+    def compress_sealed_into(self, x, kind, buf, out_len, result, scratch=None, check_block: int = 65536,
+                             chunk_blocks: int = 0) -> int:
+        """The record of `x` at buf[0], then the existing compress_*_into
+        straight to the record's end: no synchronisation, no copy of the
+        container.  `buf` >= sealed_bound bytes, `out_len` one int64 (the
+        CONTAINER's length), `result` two int32, `scratch` as the plane or
+        delta call's.  Returns the record's size: the buffer's length is that
+        plus out_len."""
+        self._sealed_kind(x, kind)
+        rec = self.check_bytes(self._content_bytes(x), check_block)
+        self.check_build_into(x, buf[:rec], check_block)
+        if kind == "frame":
+            self.compress_frame_into(x, buf[rec:], out_len, result, chunk_blocks)
+        elif kind == "planes":
+            self.compress_planes_into(x, scratch, buf[rec:], out_len, result, chunk_blocks)
+        else:
+            self.compress_delta_into(x, scratch, buf[rec:], out_len, result, chunk_blocks)
+        return rec
+
+    def compress_sealed(self, x, kind: str = "frame", check_block: int = 65536, chunk_blocks: int = 0):
+        """Compress a contiguous device tensor into one sealed buffer (a check
+        record, then a frame, plane frame or delta frame): a uint8 device
+        tensor of its exact length.  One synchronisation, to read the length."""
+        t = self.torch
+        w = self._sealed_kind(x, kind)
+        scratch = None
+        if kind != "frame":
+            need = (self.planes_scratch_bytes if kind == "planes" else self.delta_scratch_bytes)(x.numel(), w)
+            scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        buf = t.empty(self.sealed_bound(x, kind, check_block), dtype=t.uint8, device=self.device)
+        out_len = t.zeros(1, dtype=t.int64, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        rec = self.compress_sealed_into(x, kind, buf, out_len, result, scratch, check_block, chunk_blocks)
+        return buf[: rec + int(out_len.item())]
+
+    @staticmethod
+    def sealed_info(buf):
+        """`fsehip_sealed_read_header` of a sealed buffer given as bytes, a
+        numpy array or a tensor (the record and the container's first 48 bytes
+        come to the host): (CheckInfo, kind, inner_off) with kind 'frame',
+        'planes' or 'delta' and the container at buf[inner_off:]; raises
+        FseError (BAD_FRAME) otherwise."""
+        info = BlockCodec.check_info(buf)
+        upto = 32 + 4 * info.n_cb + 48
+        if hasattr(buf, "data_ptr"):  # a torch tensor
+            head = buf[:upto].cpu().numpy().tobytes()
+        else:
+            head = bytes(memoryview(buf)[:upto])
+        a = np.frombuffer(head, dtype=np.uint8)
+        kind, off = C.c_uint32(0), C.c_uint64(0)
+        check(load().fsehip_sealed_read_header(_p(a), len(a), C.byref(info), C.byref(kind), C.byref(off)),
+              "fsehip_sealed_read_header")
+        return info, SEALED_KINDS[kind.value], int(off.value)
+
+    def _sealed_dtype(self, kind: str, inner, dtype):
+        """The dtype a sealed buffer decodes to: uint8 for a frame, `dtype`
+        (default: the integer of the container's element width) otherwise."""
+        t = self.torch
+        if kind == "frame":
+            if dtype is not None and t.empty(0, dtype=dtype).element_size() != 1:
+                raise ValueError(f"dtype {dtype}: a sealed frame holds bytes")
+            return dtype or t.uint8
+        w = (self.planes_info if kind == "planes" else self.delta_info)(inner)[0].elem_bytes
+        return dtype or {1: t.uint8, 2: t.int16, 4: t.int32, 8: t.int64}[w]
+
+    def sealed_inner_info(self, kind: str, inner):
+        """The container's own header(s) at the start of `inner` (bytes, numpy
+        or a tensor): FrameInfo for a frame, (PlanesInfo | DeltaInfo,
+        FrameInfo) otherwise."""
+        return {"frame": self.frame_info, "planes": self.planes_info, "delta": self.delta_info}[kind](inner)
+
+    def decompress_sealed_into(self, buf, sealed, inner_info, out, block_status, result, check_status, check_result,
+                               scratch=None, chunk_blocks: int = 0) -> None:
+        """The existing decompress_*_into of the container, then
+        `fsehip_check_verify` on the output; no synchronisation.  `sealed` is
+        what sealed_info gave for the buffer, `inner_info` what
+        sealed_inner_info gave for its container; `out`, `block_status`,
+        `result` and `scratch` as the container's call, `check_status`
+        sealed[0].n_cb int32, `check_result` two int32."""
+        info, kind, off = sealed
+        inner = buf[off:]
+        if kind == "frame":
+            self.decompress_frame_into(inner, inner_info, out, block_status, result, chunk_blocks)
+        elif kind == "planes":
+            self.decompress_planes_into(inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
+        else:
+            self.decompress_delta_into(inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
+        self.check_verify_into(buf, info, out, check_status, check_result)
+
+    def decompress_sealed(self, buf, dtype=None, chunk_blocks: int = 0, with_result: bool = False):
+        """Decode a sealed buffer (a uint8 device tensor) with the existing
+        decompress of its container, then verify the output against the
+        record: (out, block_status, check_status), or with_result=True
+        (out, block_status, check_status, result) with the verify's two int32
+        (result[0]: OK, CHECKSUM of the whole content; result[1]: failed check
+        blocks).  Raises FseError for a buffer-level error (BAD_FRAME)."""
+        t = self.torch
+        sealed = info, kind, off = self.sealed_info(buf)
+        inner_info = self.sealed_inner_info(kind, buf[off:])
+        dt = self._sealed_dtype(kind, buf[off:], dtype)
+        scratch = None
+        if kind == "frame":
+            finfo = inner_info
+            out = t.empty(info.n_content, dtype=dt, device=self.device)
+        else:
+            self._check_dtype(inner_info[0], dt, "plane" if kind == "planes" else "delta")
+            finfo = inner_info[1]
+            scratch = t.empty(finfo.n_total, dtype=t.uint8, device=self.device)
+            out = t.empty(inner_info[0].n_elems, dtype=dt, device=self.device)
+        block_status = t.zeros(finfo.n_blocks, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        check_status = t.zeros(info.n_cb, dtype=t.int32, device=self.device)
+        check_result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_sealed_into(buf, sealed, inner_info, out, block_status, result, check_status, check_result,
+                                    scratch, chunk_blocks)
+        check(int(result[0].item()), f"sealed {kind}")
+        if int(check_result[0].item()) == -19:  # the record on the device is not the one the host read
+            raise FseError(-19, "check record")
+        if with_result:
+            return out, block_status, check_status, check_result
+        return out, block_status, check_status
+
+    def decompress_sealed_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0):
+        """Decode the ranges [(off, count), ...] of a sealed buffer without
+        decoding the rest -- elements of `dtype` when the container is a plane
+        or delta frame, bytes (dtype None or a 1-byte one) for a frame -- and
+        verify the check blocks each range wholly covers.  Returns (views, one
+        per range, of one packed tensor; the container's range statuses; the
+        check's range statuses, OK or CHECKSUM).  Raises FseError for a
+        buffer-level error (BAD_FRAME)."""
+        t = self.torch
+        info, kind, off = self.sealed_info(buf)
+        inner = buf[off:]
+        dt = self._sealed_dtype(kind, inner, dtype)
+        w = t.empty(0, dtype=dt).element_size()
+        packed, at = [], 0
+        for s, n in ranges:
+            packed.append((s, n, at))
+            at += n
+        out = t.empty(at, dtype=dt, device=self.device)
+        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        if kind == "frame":
+            self.decompress_frame_ranges_into(inner, self.frame_info(inner), packed, out, status, result, chunk_blocks)
+        else:
+            pinfo, finfo = (self.planes_info if kind == "planes" else self.delta_info)(inner)
+            self._check_dtype(pinfo, dt, "plane" if kind == "planes" else "delta")
+            arr = self.planes_ranges(packed)
+            need = (self.planes_ranges_scratch_bytes if kind == "planes" else self.delta_ranges_scratch_bytes)(w, arr)
+            scratch = t.empty(max(need, 16), dtype=t.uint8, device=self.device)
+            call = self.decompress_planes_ranges_into if kind == "planes" else self.decompress_delta_ranges_into
+            call(inner, pinfo, finfo, arr, scratch, out, status, result, chunk_blocks)
+        check(int(result[0].item()), f"sealed {kind}")
+        check_status = t.zeros(len(packed), dtype=t.int32, device=self.device)
+        check_result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.check_verify_ranges_into(buf, info, [(s * w, n * w, d * w) for s, n, d in packed], out, check_status,
+                                      check_result)
+        check(int(check_result[0].item()), "check record")
+        return [out[d: d + n] for _, n, d in packed], status, check_status
+
+    def decompress_sealed_range(self, buf, dtype, off: int, count: int, chunk_blocks: int = 0):
+        """One range of a sealed buffer as a tensor; raises FseError for a
+        buffer-level error, with the status of the first failed block the
+        range touches, or with CHECKSUM when a check block the range wholly
+        covers fails."""
+        views, status, check_status = self.decompress_sealed_ranges(buf, dtype, [(off, count)], chunk_blocks)
+        check(int(status[0].item()), "sealed range")
+        check(int(check_status[0].item()), "sealed range")
+        return views[0]
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -1227,6 +1506,68 @@ def delta_decompress(data, dtype, device=None) -> np.ndarray:
         b = int(np.flatnonzero(st)[0])
         raise FseError(int(st[b]), f"delta frame block {b}")
     return out.cpu().numpy().view(dt)
+
+
+# ---------------------------------------------------------------- sealed buffers
+def crc32(data, crc: int = 0) -> int:
+    """`fsehip_crc32`: zlib.crc32(data, crc), computed by the library on the host (no device)."""
+    a = _buf(data)
+    return int(load().fsehip_crc32(crc & 0xFFFFFFFF, _p(a) if len(a) else None, len(a))) if len(a) else crc & 0xFFFFFFFF
+
+
+def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
+    """`fsehip_crc32_combine`: the CRC-32 of A || B from crc32(A), crc32(B) and len(B) (no device)."""
+    return int(load().fsehip_crc32_combine(crc1 & 0xFFFFFFFF, crc2 & 0xFFFFFFFF, len2))
+
+
+def sealed_compress(data, kind: str = "frame", check_block: int = 65536, block_size: int = 65536, table_log: int = 0,
+                    ckpt_interval: int = 128, nstates: int = 2, device=None) -> bytes:
+    """Compress a host buffer into one sealed buffer (fsehip.h section 2f) on
+    the GPU: bytes or any numpy array for kind 'frame', a numpy array of item
+    size 2, 4 or 8 for 'planes' and of 1, 2, 4 or 8 for 'delta'."""
+    import torch
+
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    if kind == "frame":
+        a = _buf(data) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
+    else:
+        a = np.ascontiguousarray(data)
+        if a.dtype.itemsize not in _INT_VIEW:
+            raise ValueError(f"item size {a.dtype.itemsize}: 1, 2, 4 or 8 bytes")
+        a = a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize])
+    src = torch.from_numpy(a.copy()).to(codec.device)
+    return codec.compress_sealed(src, kind, check_block).cpu().numpy().tobytes()
+
+
+def sealed_decompress(blob, dtype=None, device=None):
+    """Decode a sealed buffer held in host memory: bytes for a sealed frame, a
+    1-D numpy array of `dtype` (default: the integer of the element width) for
+    a plane or delta frame.  Raises FseError on a buffer-level error
+    (BAD_FRAME), with the first failed block's status, and with CHECKSUM when
+    a check block or the whole content's CRC-32 fails."""
+    import torch
+
+    codec = BlockCodec(device=device)
+    info, kind, off = BlockCodec.sealed_info(_buf(blob))  # not a sealed buffer: BAD_FRAME before any device work
+    buf = torch.from_numpy(_buf(blob).copy()).to(codec.device)
+    dt = None if dtype is None else np.dtype(dtype)
+    out, status, check_status, result = codec.decompress_sealed(buf, None, with_result=True)
+    if dt is not None and dt.itemsize != out.element_size():
+        raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the sealed buffer holds {out.element_size()}-byte ones")
+    st = status.cpu().numpy()
+    if st.any():
+        b = int(np.flatnonzero(st)[0])
+        raise FseError(int(st[b]), f"sealed {kind} block {b}")
+    cs, res = check_status.cpu().numpy(), result.cpu().numpy()
+    if cs.any():
+        b = int(np.flatnonzero(cs)[0])
+        raise FseError(int(cs[b]), f"sealed {kind} check block {b}")
+    check(int(res[0]), f"sealed {kind} content")
+    host = out.cpu().numpy()
+    if kind == "frame" and dt is None:
+        return host.tobytes()
+    return host.view(dt) if dt is not None else host
 
 
 # ---------------------------------------------------------------- shared-table coding
@@ -1375,4 +1716,5 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "encode_table_new", "frame_compress", "frame_decompress", "frame_decompress_range",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal", "SharedTable", "norm_histogram_try_from",
-           "planes_compress", "planes_decompress", "delta_compress", "delta_decompress"]
+           "planes_compress", "planes_decompress", "delta_compress", "delta_decompress",
+           "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo"]

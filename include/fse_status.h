@@ -74,5 +74,9 @@
  * table_len.  The crate's Encoder::encode indexes its tables unchecked there
  * (fse.rs:231-238).                                                          */
 #define FSE_ERR_SYMBOL_NOT_IN_TABLE (-20)
+/* The check record (fsehip.h section 2f): the CRC-32 of a check block's
+ * content, or of the whole content, differs from the recorded one -- the
+ * bytes that came back are not the bytes that went in.                      */
+#define FSE_ERR_CHECKSUM (-21)
 
 #endif

@@ -1051,6 +1051,148 @@ int fsehip_delta_decompress_ranges(const fsehip_delta_info* info, const fsehip_f
                                    int32_t* d_result, fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * (2f) The check record and sealed buffers: per-block CRC-32 of the content
+ *
+ * The containers of sections 2b, 2d and 2e tell a reader what the format can
+ * see (a bad header, a missing marker, a checkpoint that disagrees); a RAW
+ * record is copied unchecked, and an FSE payload with a flipped bit very
+ * often still decodes with FSE_OK.  The check record holds CRC-32s of the
+ * CONTENT -- what the user handed in and gets back; for a plane or delta
+ * frame the tensor's n_elems * w bytes, not the image -- one per check block,
+ * and travels in front of an unchanged container.  Version 1; integers
+ * little-endian, no padding, any byte address:
+ *
+ *   header, 32 bytes
+ *      0  u8[4] magic "FSEK"
+ *      4  u8    version = 1
+ *      5  u8    algorithm = 1   (FSEHIP_CHECK_CRC32)
+ *      6  u8    check_log       log2 of check_block, 8..16 (256 B .. 64 KiB)
+ *      7  u8    0
+ *      8  u64   n_content       bytes of content
+ *     16  u32   n_cb            = ceil(n_content / check_block); 0 when empty
+ *     20  u32   content_crc     CRC-32 of the whole content; 0 when empty
+ *     24  u32   reserved = 0
+ *     28  u32   header_crc      CRC-32 of bytes 0..27
+ *   table, n_cb x u32: CRC-32 of content[b * check_block,
+ *                                        min((b + 1) * check_block, n_content))
+ *
+ * The CRC is zlib's: reflected polynomial 0xEDB88320, initial value and final
+ * XOR 0xFFFFFFFF, so content_crc = zlib.crc32(content) and any reader can
+ * check it.  CRCs combine exactly, crc(A || B) = crc(A) * x^(8 |B|) mod P xor
+ * crc(B), so content_crc is the combine of the table and costs no second
+ * pass, damage is localised to one check block, and a range read can verify
+ * the blocks it covers.  A small check_log buys finer coverage -- of damage
+ * and of ranges -- at 4 bytes per check block: 4 / 2^check_log of the content
+ * (0.006 % at 16, 1.6 % at 8).
+ *
+ * A SEALED BUFFER is a check record followed directly by exactly one
+ * container of section 2b, 2d or 2e; the container's magic says which.  The
+ * container's content length (n_total; n_elems * w) must equal n_content and
+ * the buffer ends with the container: anything else is BAD_FRAME.  The
+ * record's size is known before anything runs, so the container is
+ * compressed straight to its final place, fsehip_check_bytes into the buffer.
+ * Nothing in sections 2b, 2d or 2e changes.
+ * ------------------------------------------------------------------------ */
+
+#define FSEHIP_CHECK_CRC32 1u
+#define FSEHIP_SEALED_FRAME 0u  /* `kind` of fsehip_sealed_read_header */
+#define FSEHIP_SEALED_PLANES 1u
+#define FSEHIP_SEALED_DELTA 2u
+
+typedef struct {
+    uint32_t version, algorithm, check_log, reserved; /* reserved: byte 7 | the word at 24 */
+    uint64_t n_content;
+    uint32_t n_cb, content_crc;
+    uint32_t header_crc, pad_; /* pad_ is not stored */
+} fsehip_check_info;
+
+/* zlib's crc32(crc, buf, len) and crc32_combine(crc1, crc2, len2), host
+ * memory, no device: fsehip_crc32(0, NULL, 0) = 0 is the initial value,
+ * fsehip_crc32(fsehip_crc32(0, a, n), b, m) the CRC of a || b, and
+ * fsehip_crc32_combine(crc(a), crc(b), m) the same.  Part of the format, as
+ * the header readers are. */
+uint32_t fsehip_crc32(uint32_t crc, const uint8_t* buf, size_t n);
+uint32_t fsehip_crc32_combine(uint32_t crc1, uint32_t crc2, uint64_t len2);
+
+/* 32 + 4 * n_cb: the record's size for n_content bytes (check_log 0 = 16).
+ * 0 for a check_log outside 8..16 or when n_cb does not fit 32 bits. */
+uint64_t fsehip_check_bytes(uint64_t n_content, uint32_t check_log);
+/* Parse and validate the first 32 bytes of a check record (host pointer; len
+ * = bytes available).  FSE_ERR_BAD_FRAME for len < 32, a bad magic, version,
+ * algorithm or check_log, a nonzero byte 7 or reserved word, an n_cb other
+ * than ceil(n_content / check_block), a nonzero content_crc with n_content =
+ * 0, or a wrong header_crc.  `out` is zeroed on every reject. */
+int fsehip_check_read_header(const uint8_t* hdr, size_t len, fsehip_check_info* out);
+/* The 32 header bytes of `info`, the host's way to make a record: header_crc
+ * is computed here (info->header_crc is not read).  BAD_ARG when the other
+ * fields would not pass fsehip_check_read_header. */
+int fsehip_check_write_header(const fsehip_check_info* info, uint8_t hdr[32]);
+/* The head of a sealed buffer (host pointer; len = bytes available, at least
+ * the record and the first 32 bytes of a frame or 48 of a plane or delta
+ * frame): the record's header into `info`, the container's kind from its
+ * magic, and *inner_off = 32 + 4 * n_cb, where the container starts.
+ * BAD_FRAME for a record fsehip_check_read_header rejects, a head too short,
+ * another magic, or a container whose content length is not n_content.  The
+ * container's header is then read with its own reader at buf + *inner_off. */
+int fsehip_sealed_read_header(const uint8_t* buf, size_t len, fsehip_check_info* info, uint32_t* kind,
+                              uint64_t* inner_off);
+
+/* Write the whole record of n_content bytes at d_content to d_record
+ * (fsehip_check_bytes(n_content, check_log) bytes; check_log 0 = 16): one CRC
+ * kernel over the content, then a finish kernel that combines the table into
+ * content_crc (a tree over runs of entries, not a serial walk) and writes the
+ * header.  d_content and d_record may have any byte alignment; the content is
+ * read in whole aligned 16-byte words that hold at least one of its bytes.
+ * n_content == 0 writes a 32-byte record.  Asynchronous on `stream`, no host
+ * synchronisation, no workspace.  Before any device use: BAD_ARG (a null
+ * d_record, a null d_content with n_content > 0), UNSUPPORTED (a check_log
+ * outside 8..16, n_cb above 2^32 - 1), NO_DEVICE. */
+int fsehip_check_build(uint32_t check_log, const uint8_t* d_content, uint64_t n_content, uint8_t* d_record,
+                       fsehip_stream_t stream);
+
+/* Compare the record at d_record, whose header fsehip_check_read_header
+ * parsed into `info`, with the n_content bytes at d_content (n_content must
+ * equal info->n_content: BAD_ARG).  The 32 header bytes on the device must
+ * equal `info`: otherwise d_result[0] = BAD_FRAME, every check status
+ * BAD_FRAME and d_result[1] = n_cb.  Otherwise d_check_status[b] (n_cb
+ * entries, required when n_cb > 0; it also holds the computed CRCs between
+ * the kernels) = FSE_OK or FSE_ERR_CHECKSUM, d_result[1] = failed check
+ * blocks, and d_result[0] = FSE_ERR_CHECKSUM when the combine of the COMPUTED
+ * block CRCs differs from content_crc, else FSE_OK.  Nothing is stored into
+ * the content or the record.  Alignment, reads and call-level statuses as
+ * fsehip_check_build (BAD_ARG also for a null or invalid `info`, a null
+ * d_result). */
+int fsehip_check_verify(const fsehip_check_info* info, const uint8_t* d_record, const uint8_t* d_content,
+                        uint64_t n_content, int32_t* d_check_status, int32_t* d_result, fsehip_stream_t stream);
+
+/* How many bytes of a range request fsehip_check_verify_ranges covers: the
+ * check blocks that lie wholly inside a range, summed over the ranges.
+ * BAD_ARG for an invalid info, or src_off + len overflowing or past
+ * n_content. */
+int fsehip_check_ranges_verified_bytes(const fsehip_check_info* info, const fsehip_frame_range* ranges,
+                                       uint32_t n_ranges, uint64_t* bytes);
+
+/* Verify decoded ranges: `ranges` are the triples of
+ * fsehip_frame_decompress_ranges in content bytes, range r's bytes lying at
+ * d_out + dst_off (any alignment).  For each range every check block that
+ * lies wholly inside [src_off, src_off + len) is verified; the content's last
+ * block counts as whole when the range ends at n_content.  Partial blocks at
+ * a range's edges are NOT verified -- they cannot be without decoding more
+ * than was asked for; a smaller check_log leaves less uncovered.
+ * d_range_status[r] (n_ranges entries, required when n_ranges > 0) = FSE_OK
+ * or FSE_ERR_CHECKSUM; d_result[0] = FSE_OK, d_result[1] = ranges with a
+ * failed check block.  A header on the device that differs from `info`:
+ * d_result[0] = BAD_FRAME, every range status BAD_FRAME, d_result[1] =
+ * n_ranges.  The ranges reach the device as kernel arguments, 32 per launch:
+ * no staging, no host synchronisation.  Before any device use: BAD_ARG (a
+ * null pointer, an invalid info, a range overflowing or past n_content,
+ * overlapping destinations of non-empty ranges), DST_TOO_SMALL (dst_off + len
+ * > out_cap), NO_DEVICE. */
+int fsehip_check_verify_ranges(const fsehip_check_info* info, const uint8_t* d_record,
+                               const fsehip_frame_range* ranges, uint32_t n_ranges, const uint8_t* d_out,
+                               uint64_t out_cap, int32_t* d_range_status, int32_t* d_result, fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
  *
  * The crate's `pub mod fse` lets a caller code any number of messages against
