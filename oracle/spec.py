@@ -212,6 +212,15 @@ def norm_table_len(norm) -> int:
 # ---------------------------------------------------------------- header
 def header_write(norm, L, table_len) -> bytes:
     """NormHistogram::write (histogram.rs:376-431)."""
+    return _header_sink(norm, L, table_len).to_bytes()
+
+
+def header_bits(norm, L, table_len) -> int:
+    """The bit count NormHistogram::write returns (writer.rs:201-222)."""
+    return len(_header_sink(norm, L, table_len).bits)
+
+
+def _header_sink(norm, L, table_len) -> BitSink:
     w = BitSink()
     w.put(L - LOG_MIN, 4)
     thr = 1 << L
@@ -245,7 +254,7 @@ def header_write(norm, L, table_len) -> bytes:
         while rem < thr:
             nb -= 1
             thr >>= 1
-    return w.to_bytes()
+    return w
 
 
 def header_read(data: bytes):

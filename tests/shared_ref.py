@@ -52,11 +52,12 @@ def try_from(table):
     return [int(x) for x in table], total.bit_length() - 1, nz[-1] + 1
 
 
-def build_status(norm, L, table_len) -> str:
-    """What fsehip_shared_table_build reports for this NormHistogram."""
+def build_status(norm, L, table_len, log_max: int = LOG_MAX_SHARED) -> str:
+    """What fsehip_shared_table_build reports for this NormHistogram
+    (log_max = 15: what the crate's EncodeTable::new accepts)."""
     if not spec.LOG_MIN <= L <= spec.LOG_MAX:
         return "TABLELOG_RANGE"
-    if L > LOG_MAX_SHARED:
+    if L > log_max:
         return "UNSUPPORTED"
     if not 1 <= table_len <= 256:
         return "BAD_TABLE"
@@ -75,12 +76,14 @@ def _tables(norm: tuple, L: int, table_len: int):
     return spec.encode_table(list(norm), L, table_len), spec.decode_table(list(norm), L, table_len)
 
 
-def compress_shared(src: bytes, norm, L: int, table_len: int, nstates: int = 2) -> tuple[bytes, int]:
+def compress_shared(src: bytes, norm, L: int, table_len: int, nstates: int = 2,
+                    log_max: int = LOG_MAX_SHARED) -> tuple[bytes, int]:
     """The payload of `src` against the table and its bit count (marker
-    included): lib.rs:151-182 at two states, fse.rs:394-421 at one."""
+    included): lib.rs:151-182 at two states, fse.rs:394-421 at one.  log_max
+    = 15 lifts the shared image's limit of 12 (the crate's Encoder has none)."""
     src = bytes(src)
     n = len(src)
-    if build_status(norm, L, table_len) != "OK":
+    if build_status(norm, L, table_len, log_max) != "OK":
         raise SpecError("BAD_TABLE")
     if n == 0:
         raise SpecError("EMPTY")
