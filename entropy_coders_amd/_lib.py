@@ -57,6 +57,9 @@ EXPORTS = (
     "fsehip_crc32", "fsehip_crc32_combine", "fsehip_check_bytes", "fsehip_check_read_header",
     "fsehip_check_write_header", "fsehip_sealed_read_header", "fsehip_check_build", "fsehip_check_verify",
     "fsehip_check_ranges_verified_bytes", "fsehip_check_verify_ranges",
+    "fsehip_log2q8", "fsehip_estimate_choose", "fsehip_estimate_block_host", "fsehip_container_kind",
+    "fsehip_estimate_image_bytes", "fsehip_image_histogram", "fsehip_estimate_blocks",
+    "fsehip_estimate_scratch_bytes", "fsehip_estimate",
 )
 
 STATUS = {
@@ -136,6 +139,17 @@ class CheckInfo(C.Structure):
     _fields_ = [("version", C.c_uint32), ("algorithm", C.c_uint32), ("check_log", C.c_uint32), ("reserved", C.c_uint32),
                 ("n_content", C.c_uint64), ("n_cb", C.c_uint32), ("content_crc", C.c_uint32),
                 ("header_crc", C.c_uint32), ("pad_", C.c_uint32)]
+
+
+KINDS = ("frame", "planes", "delta")  # FSEHIP_KIND_FRAME / _PLANES / _DELTA
+KIND_SEALED = 3                        # FSEHIP_KIND_SEALED: fsehip_container_kind of an "FSEK" buffer
+EST_NONE = (1 << 64) - 1               # FSEHIP_EST_NONE
+EST_RAW, EST_RLE, EST_FSE = 0, 1, 2    # FSEHIP_EST_*: the frame directory's block types
+
+
+class BlockEstimate(C.Structure):
+    """fsehip_block_estimate: one block's estimated type, record bytes, payload bits and table log."""
+    _fields_ = [("type", C.c_uint32), ("rec", C.c_uint32), ("bits", C.c_uint32), ("table_log", C.c_uint32)]
 
 
 class Histogram(C.Structure):
@@ -292,6 +306,18 @@ def load() -> C.CDLL:
     lib.fsehip_check_verify.argtypes = [CI, P, P, u64, P, P, P]
     lib.fsehip_check_ranges_verified_bytes.argtypes = [CI, C.POINTER(FrameRange), u32, C.POINTER(u64)]
     lib.fsehip_check_verify_ranges.argtypes = [CI, P, C.POINTER(FrameRange), u32, P, u64, P, P, P]
+    lib.fsehip_log2q8.argtypes = [u32]
+    lib.fsehip_log2q8.restype = u32
+    lib.fsehip_estimate_choose.argtypes = [C.POINTER(u64 * 3)]
+    lib.fsehip_estimate_block_host.argtypes = [P, u32, P, u32, u32, C.POINTER(FrameParams), C.POINTER(BlockEstimate)]
+    lib.fsehip_container_kind.argtypes = [P, sz]
+    lib.fsehip_estimate_image_bytes.argtypes = [u32, u64, u32]
+    lib.fsehip_estimate_image_bytes.restype = u64
+    lib.fsehip_image_histogram.argtypes = [u32, u32, P, u64, u32, P, P]
+    lib.fsehip_estimate_blocks.argtypes = [C.POINTER(FrameParams), P, u64, P, P, P, P, P, P]
+    lib.fsehip_estimate_scratch_bytes.argtypes = [u64, u32, u32, u32]
+    lib.fsehip_estimate_scratch_bytes.restype = u64
+    lib.fsehip_estimate.argtypes = [C.POINTER(FrameParams), u32, u32, P, u64, P, u64, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

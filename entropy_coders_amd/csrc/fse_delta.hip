@@ -31,46 +31,12 @@ namespace {
 constexpr uint32_t DL_GROUPS = FSEHIP_DELTA_RESTART / 16;  // 16-element groups in a restart group
 static_assert(DL_GROUPS == PL_T, "one workgroup's lanes cover exactly one restart group");
 
-struct __attribute__((packed, aligned(1))) U128b {
-    uint32_t x, y, z, w;
-};
 struct __attribute__((packed, aligned(1))) U64b {
     uint32_t x, y;
 };
 struct __attribute__((packed, aligned(1))) U16b {
     uint16_t v;
 };
-
-// the integer the sums run in
-template <int W>
-struct Acc {
-    using type = uint32_t;
-};
-template <>
-struct Acc<8> {
-    using type = uint64_t;
-};
-
-// element i (a constant after unrolling) of the lane's 4 W dwords
-template <int W>
-__device__ __forceinline__ typename Acc<W>::type get(const uint32_t (&e)[4 * W], int i) {
-    if constexpr (W == 1) return (e[i >> 2] >> (8 * (i & 3))) & 0xFFu;
-    else if constexpr (W == 2) return (e[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
-    else if constexpr (W == 4) return e[i];
-    else return (uint64_t)e[2 * i] | ((uint64_t)e[2 * i + 1] << 32);
-}
-
-// the low 8 W bits of v into element i; the dwords start out zero for W < 4
-template <int W>
-__device__ __forceinline__ void put(uint32_t (&e)[4 * W], int i, typename Acc<W>::type v) {
-    if constexpr (W == 1) e[i >> 2] |= (v & 0xFFu) << (8 * (i & 3));
-    else if constexpr (W == 2) e[i >> 1] |= (v & 0xFFFFu) << (16 * (i & 1));
-    else if constexpr (W == 4) e[i] = v;
-    else {
-        e[2 * i] = (uint32_t)v;
-        e[2 * i + 1] = (uint32_t)(v >> 32);
-    }
-}
 
 template <int CTRL, int ROWS>
 __device__ __forceinline__ uint64_t dpp0_64(uint64_t v) {
@@ -153,6 +119,9 @@ __global__ __launch_bounds__(PL_T) void delta_split_kernel(const uint8_t* __rest
         // source bytes of the group; in the ragged last one whole dwords that
         // hold one are loaded (up to roundup(n_elems * W, 4), never more)
         const uint32_t rem = whole ? 16u * W : (uint32_t)(n_elems - (g << 4)) * W;
+        // (the load, the deltas and the pad below are load_group, delta_zigzag
+        // and zero_pad of fse_planes_dev.hpp written out: this kernel's code
+        // is kept as it was measured)
         uint32_t e[4 * W];
         if (whole) {
             if constexpr (W == 1) {

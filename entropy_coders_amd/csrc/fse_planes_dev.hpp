@@ -1,8 +1,9 @@
 // fse_planes_dev.hpp -- the device pieces the plane transforms (fse_planes.hip,
-// fsehip.h section 2d) and the delta transforms (fse_delta.hip, section 2e)
-// share: the launch shape, the under-aligned access types and the byte
-// transposes on v_perm_b32.  Element i of a 16-element group is the dwords
-// [i * W / 4, (i + 1) * W / 4) of the lane's 4 W.
+// fsehip.h section 2d), the delta transforms (fse_delta.hip, section 2e) and
+// the image histogram (fse_estimate.hip, section 2g) share: the launch shape,
+// the under-aligned access types, the byte transposes on v_perm_b32, and the
+// group load and zigzag delta of the element side.  Element i of a 16-element
+// group is the dwords [i * W / 4, (i + 1) * W / 4) of the lane's 4 W.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -23,6 +24,9 @@ struct __attribute__((packed, aligned(2))) U128u {
 };
 struct __attribute__((packed, aligned(1))) U32u {
     uint32_t v;
+};
+struct __attribute__((packed, aligned(1))) U128b {
+    uint32_t x, y, z, w;
 };
 
 // bytes of {hi, lo} picked by sel: selector 0..3 = lo's bytes, 4..7 = hi's
@@ -85,6 +89,106 @@ __device__ __forceinline__ void interleave(const uint32_t (&p)[W][4], uint32_t (
 #pragma unroll
                 for (int j = 0; j < 4; ++j) e[(4 * q + j) * D + h] = t[j];
             }
+    }
+}
+
+// ---- the element side of the delta transforms (fse_delta.hip) and of the
+// image histogram (fse_estimate.hip)
+
+// the integer the sums run in
+template <int W>
+struct Acc {
+    using type = uint32_t;
+};
+template <>
+struct Acc<8> {
+    using type = uint64_t;
+};
+
+// element i (a constant after unrolling) of the lane's 4 W dwords
+template <int W>
+__device__ __forceinline__ typename Acc<W>::type get(const uint32_t (&e)[4 * W], int i) {
+    if constexpr (W == 1) return (e[i >> 2] >> (8 * (i & 3))) & 0xFFu;
+    else if constexpr (W == 2) return (e[i >> 1] >> (16 * (i & 1))) & 0xFFFFu;
+    else if constexpr (W == 4) return e[i];
+    else return (uint64_t)e[2 * i] | ((uint64_t)e[2 * i + 1] << 32);
+}
+
+// the low 8 W bits of v into element i; the dwords start out zero for W < 4
+template <int W>
+__device__ __forceinline__ void put(uint32_t (&e)[4 * W], int i, typename Acc<W>::type v) {
+    if constexpr (W == 1) e[i >> 2] |= (v & 0xFFu) << (8 * (i & 3));
+    else if constexpr (W == 2) e[i >> 1] |= (v & 0xFFFFu) << (16 * (i & 1));
+    else if constexpr (W == 4) e[i] = v;
+    else {
+        e[2 * i] = (uint32_t)v;
+        e[2 * i + 1] = (uint32_t)(v >> 32);
+    }
+}
+
+// The 16 elements of one group at s (aligned to W).  A whole group is W
+// 16-byte loads; of the ragged last one, `rem` < 16 W source bytes, whole
+// dwords that hold one are loaded (up to roundup(n_elems * W, 4), never
+// more) and the rest is zero.
+template <int W>
+__device__ __forceinline__ void load_group(const uint8_t* __restrict__ s, bool whole, uint32_t rem,
+                                           uint32_t (&e)[4 * W]) {
+    if (whole) {
+        if constexpr (W == 1) {
+            const U128b v = *reinterpret_cast<const U128b*>(s);
+            e[0] = v.x;
+            e[1] = v.y;
+            e[2] = v.z;
+            e[3] = v.w;
+        } else {
+#pragma unroll
+            for (int j = 0; j < W; ++j) {
+                const U128u v = *reinterpret_cast<const U128u*>(s + 16 * j);
+                e[4 * j] = v.x;
+                e[4 * j + 1] = v.y;
+                e[4 * j + 2] = v.z;
+                e[4 * j + 3] = v.w;
+            }
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4 * W; ++j) e[j] = 4u * j < rem ? reinterpret_cast<const U32u*>(s + 4 * j)->v : 0u;
+    }
+}
+
+// the pad of a ragged group, and whatever its last loaded dword held behind
+// the source, to zero
+template <int W>
+__device__ __forceinline__ void zero_pad(uint32_t (&z)[4 * W], uint32_t rem) {
+#pragma unroll
+    for (int j = 0; j < 4 * W; ++j) {
+        if (4u * j >= rem) z[j] = 0;
+        else if (4u * j + 4u > rem) z[j] &= (1u << (8u * (rem - 4u * j))) - 1u;
+    }
+}
+
+// The zigzag deltas z of the group's elements e; the element before the
+// lane's first is read at s - W (a line the neighbouring lane loads anyway)
+// and is zero at a restart.
+template <int W>
+__device__ __forceinline__ void delta_zigzag(const uint8_t* __restrict__ s, bool restart, const uint32_t (&e)[4 * W],
+                                             uint32_t (&z)[4 * W]) {
+    using A = typename Acc<W>::type;
+    A prev = 0;
+    if (!restart) {
+        if constexpr (W == 1) prev = s[-1];
+        else if constexpr (W == 2) prev = *reinterpret_cast<const uint16_t*>(s - 2);
+        else if constexpr (W == 4) prev = *reinterpret_cast<const uint32_t*>(s - 4);
+        else prev = *reinterpret_cast<const uint64_t*>(s - 8);
+    }
+#pragma unroll
+    for (int j = 0; j < 4 * W; ++j) z[j] = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        const A x = get<W>(e, i);
+        const A d = x - prev;
+        prev = x;
+        put<W>(z, i, (A)(d << 1) ^ (A)(0 - ((d >> (8 * W - 1)) & 1u)));
     }
 }
 

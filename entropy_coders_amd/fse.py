@@ -11,9 +11,9 @@ import threading
 
 import numpy as np
 
-from ._lib import (SEALED_KINDS, BitStackReaderState, BitStackWriterState, BitStreamReaderState, CheckInfo, DecodeTable,
-                   DeltaInfo, EncodeTable, FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params,
-                   PlanesInfo, PlanesRange, check, load)
+from ._lib import (EST_NONE, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState, BitStackWriterState,
+                   BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, EncodeTable, FrameInfo, FrameParams,
+                   FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check, load)
 
 
 def _buf(data) -> np.ndarray:
@@ -1382,6 +1382,144 @@ class BlockCodec:
         check(int(check_status[0].item()), "sealed range")
         return views[0]
 
+    # ------------------------------------------------------------ the size estimate
+    # fsehip.h section 2g: the length each container would have, from the
+    # block histograms of its image and the encoder's own normalisation, and
+    # the automatic choice among compress_frame / compress_planes /
+    # compress_delta.  Kinds are "frame", "planes", "delta" (or 0, 1, 2).
+    @staticmethod
+    def _kind(kind) -> int:
+        k = KINDS.index(kind) if isinstance(kind, str) and kind in KINDS else kind
+        if k not in (0, 1, 2):
+            raise ValueError(f"kind {kind!r}: one of {KINDS}")
+        return k
+
+    @staticmethod
+    def _estimate_elem_bytes(x) -> int:
+        w = x.element_size()
+        if w not in (1, 2, 4, 8):
+            raise ValueError(f"element size {w}: the containers take 1, 2, 4 or 8 bytes")
+        if not x.is_contiguous():
+            raise ValueError("the estimate needs a contiguous tensor")
+        return w
+
+    def _kind_mask(self, kinds) -> int:
+        """Bit k for every kind asked for (None: all three); a kind that does
+        not take the width stays in the mask and is estimated as EST_NONE."""
+        mask = 0
+        for kind in (KINDS if kinds is None else kinds):
+            mask |= 1 << self._kind(kind)
+        if mask == 0:
+            raise ValueError("no kind asked for")
+        return mask
+
+    def _frame_params(self, chunk_blocks: int = 0) -> FrameParams:
+        return FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
+                           chunk_blocks)
+
+    def image_histogram(self, x, kind):
+        """`fsehip_image_histogram`: the 256-bin byte counts of every block
+        (the codec's block size) of the image the container of `kind` codes
+        for the contiguous device tensor x -- its raw bytes, its plane image
+        or its delta image, the images themselves never written.  A uint32
+        device tensor [n_blocks, 256]; no synchronisation."""
+        t = self.torch
+        w, k = self._estimate_elem_bytes(x), self._kind(kind)
+        n_image = int(self.lib.fsehip_estimate_image_bytes(k, x.numel(), w))
+        counts = t.zeros((self.n_blocks(n_image), 256), dtype=t.int32, device=self.device).view(t.uint32)
+        check(self.lib.fsehip_image_histogram(k, w, C.c_void_p(x.data_ptr()), x.numel(), self.block_size,
+                                              C.c_void_p(counts.data_ptr()), self._stream()), "fsehip_image_histogram")
+        return counts
+
+    def estimate_blocks(self, counts, n_image: int) -> dict:
+        """`fsehip_estimate_blocks` for a [n_blocks, 256] uint32 (or int32)
+        device tensor of counts of an image of n_image bytes, under the
+        codec's table log, checkpoint interval and nstates: device tensors
+        `type` (uint8: 0 RAW, 1 RLE, 2 FSE), `rec` (int32 record bytes),
+        `bits` (int32 payload bits), `log` (uint8) per block and `total` (one
+        int64: the frame's estimated length).  No synchronisation."""
+        t = self.torch
+        nb = self.n_blocks(n_image)
+        out = {"type": t.zeros(nb, dtype=t.uint8, device=self.device),
+               "rec": t.zeros(nb, dtype=t.int32, device=self.device),
+               "bits": t.zeros(nb, dtype=t.int32, device=self.device),
+               "log": t.zeros(nb, dtype=t.uint8, device=self.device),
+               "total": t.zeros(1, dtype=t.int64, device=self.device)}
+        p = self._frame_params()
+        check(self.lib.fsehip_estimate_blocks(
+            C.byref(p), C.c_void_p(counts.data_ptr()), n_image, C.c_void_p(out["type"].data_ptr()),
+            C.c_void_p(out["rec"].data_ptr()), C.c_void_p(out["bits"].data_ptr()), C.c_void_p(out["log"].data_ptr()),
+            C.c_void_p(out["total"].data_ptr()), self._stream()), "fsehip_estimate_blocks")
+        return out
+
+    def estimate_scratch_bytes(self, x, kinds=None) -> int:
+        """`fsehip_estimate_scratch_bytes` for x and the kinds asked for."""
+        w = self._estimate_elem_bytes(x)
+        return int(self.lib.fsehip_estimate_scratch_bytes(x.numel(), w, self._kind_mask(kinds), self.block_size))
+
+    def estimate_into(self, x, scratch, est, kinds=None) -> None:
+        """`fsehip_estimate`, no synchronisation: `scratch` a uint8 device
+        tensor of >= estimate_scratch_bytes (16-byte aligned), `est` three
+        int64 on the device, est[k] = the estimated length of kind k or -1
+        (FSEHIP_EST_NONE read as int64) for a kind not asked for or not
+        taking the element width."""
+        w = self._estimate_elem_bytes(x)
+        p = self._frame_params()
+        check(self.lib.fsehip_estimate(
+            C.byref(p), self._kind_mask(kinds), w, C.c_void_p(x.data_ptr()), x.numel(),
+            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(est.data_ptr()), self._stream()),
+            "fsehip_estimate")
+
+    def estimate(self, x, kinds=None) -> dict:
+        """The estimated container length of a contiguous device tensor for
+        each kind of `kinds` (None: all that take its element width): a dict
+        kind name -> bytes, under the codec's block size, table log,
+        checkpoint interval and nstates.  One synchronisation: the 24-byte
+        copy of the three estimates to the host."""
+        t = self.torch
+        scratch = t.empty(max(self.estimate_scratch_bytes(x, kinds), 16), dtype=t.uint8, device=self.device)
+        est = t.zeros(3, dtype=t.int64, device=self.device)
+        self.estimate_into(x, scratch, est, kinds)
+        host = est.cpu().numpy().view(np.uint64)
+        return {KINDS[k]: int(host[k]) for k in range(3) if int(host[k]) != EST_NONE}
+
+    def compress_auto(self, x, kinds=None, chunk_blocks: int = 0):
+        """Estimate, choose (`estimate_choose`: the smallest, ties to frame,
+        then planes, then delta) and compress: (buf, kind name), buf exactly
+        what compress_frame / compress_planes / compress_delta returns for
+        that kind.  The frame codes the tensor's bytes.  Two synchronisations:
+        the estimate's and the length's."""
+        est = self.estimate(x, kinds)
+        kind = estimate_choose(est)
+        if kind == "frame":
+            t = self.torch  # (an empty tensor has no stride to view through)
+            raw = x.reshape(-1).view(t.uint8) if x.numel() else t.empty(0, dtype=t.uint8, device=self.device)
+            return self.compress_frame(raw, chunk_blocks), kind
+        if kind == "planes":
+            return self.compress_planes(x, chunk_blocks), kind
+        return self.compress_delta(x, chunk_blocks), kind
+
+    def decompress_auto(self, buf, dtype, chunk_blocks: int = 0):
+        """Decode a frame, plane frame or delta frame (a uint8 device tensor)
+        by its magic into a 1-D tensor of `dtype`: (out, block_status) as
+        decompress_frame / decompress_planes / decompress_delta.  A frame's
+        bytes are viewed as `dtype` (ValueError when they are no whole number
+        of elements)."""
+        kind = container_kind(buf)
+        if kind == "planes":
+            return self.decompress_planes(buf, dtype, chunk_blocks)
+        if kind == "delta":
+            return self.decompress_delta(buf, dtype, chunk_blocks)
+        if kind != "frame":
+            raise ValueError("a sealed buffer goes to decompress_sealed")
+        out, status = self.decompress_frame(buf, chunk_blocks)
+        w = self.torch.empty(0, dtype=dtype).element_size()
+        if out.numel() % w:
+            raise ValueError(f"the frame holds {out.numel()} bytes, no whole number of {dtype} elements")
+        if out.numel() == 0:
+            return self.torch.empty(0, dtype=dtype, device=self.device), status
+        return out.view(dtype), status
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -1506,6 +1644,76 @@ def delta_decompress(data, dtype, device=None) -> np.ndarray:
         b = int(np.flatnonzero(st)[0])
         raise FseError(int(st[b]), f"delta frame block {b}")
     return out.cpu().numpy().view(dt)
+
+
+# ---------------------------------------------------------------- the size estimate and the automatic choice
+def log2q8(c: int) -> int:
+    """`fsehip_log2q8`: the estimate's 256 * log2(c) for 1 <= c <= 32768 (host, no device)."""
+    if not 1 <= c <= 32768:
+        raise ValueError(f"log2q8({c}): 1..32768")
+    return int(load().fsehip_log2q8(c))
+
+
+def estimate_choose(est):
+    """`fsehip_estimate_choose`: the kind name of the smallest estimate of a
+    dict kind name -> bytes (BlockCodec.estimate's) or a 3-sequence indexed by
+    kind with EST_NONE for a missing one; ties go to frame, then planes, then
+    delta.  ValueError when there is nothing to choose from."""
+    if isinstance(est, dict):
+        est = [est.get(name, EST_NONE) for name in KINDS]
+    arr = (C.c_uint64 * 3)(*[int(v) for v in est])
+    k = load().fsehip_estimate_choose(C.byref(arr))
+    if k < 0:
+        raise ValueError("no estimate to choose from")
+    return KINDS[k]
+
+
+def container_kind(buf) -> str:
+    """`fsehip_container_kind`: "frame", "planes", "delta" or "sealed" from
+    the magic of a container given as bytes, a numpy array or a tensor (its
+    first 4 bytes come to the host); raises FseError (BAD_FRAME) for anything
+    else."""
+    if hasattr(buf, "data_ptr"):  # a torch tensor
+        head = buf[:4].cpu().numpy().tobytes()
+    else:
+        head = bytes(memoryview(buf)[:4])
+    a = np.frombuffer(head, dtype=np.uint8)
+    k = load().fsehip_container_kind(_p(a), len(a))
+    if k < 0:
+        raise FseError(k, "fsehip_container_kind")
+    return "sealed" if k == KIND_SEALED else KINDS[k]
+
+
+def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
+                  nstates: int = 2, device=None):
+    """Compress a numpy array of item size 1, 2, 4 or 8 into whichever of the
+    frame, the plane frame and the delta frame the estimate finds smallest
+    (BlockCodec.compress_auto) on the GPU; copies through torch.  Returns
+    (bytes, kind name)."""
+    import torch
+
+    a = np.ascontiguousarray(data)
+    if a.dtype.itemsize not in _INT_VIEW:
+        raise ValueError(f"item size {a.dtype.itemsize}: the containers take 1, 2, 4 or 8 bytes")
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    src = torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device)
+    buf, kind = codec.compress_auto(src, kinds)
+    return buf.cpu().numpy().tobytes(), kind
+
+
+def auto_decompress(blob, dtype, device=None) -> np.ndarray:
+    """Decode what auto_compress returned, by its magic, into a 1-D numpy
+    array of `dtype`; raises FseError as frame_decompress / planes_decompress
+    / delta_decompress."""
+    kind = container_kind(_buf(blob))
+    if kind == "planes":
+        return planes_decompress(blob, dtype, device)
+    if kind == "delta":
+        return delta_decompress(blob, dtype, device)
+    if kind != "frame":
+        raise ValueError("a sealed buffer goes to sealed_decompress")
+    return np.frombuffer(frame_decompress(blob, device), dtype=np.dtype(dtype))
 
 
 # ---------------------------------------------------------------- sealed buffers
@@ -1717,4 +1925,5 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal", "SharedTable", "norm_histogram_try_from",
            "planes_compress", "planes_decompress", "delta_compress", "delta_decompress",
-           "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo"]
+           "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo",
+           "auto_compress", "auto_decompress", "container_kind", "estimate_choose", "log2q8"]

@@ -1193,6 +1193,167 @@ int fsehip_check_verify_ranges(const fsehip_check_info* info, const uint8_t* d_r
                                uint64_t out_cap, int32_t* d_range_status, int32_t* d_result, fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
+ * (2g) Size estimates: which of the frame, the plane frame and the delta
+ *      frame is smallest for a tensor, without compressing it
+ *
+ * A wrong container costs up to 3.4x in size; finding
+ * the right one by compressing three times costs three encodes and three
+ * output buffers.  The estimate predicts each container's length from the
+ * 256-bin byte counts of every block of its image -- the raw bytes, the plane
+ * image (section 2d) or the delta image (section 2e), the latter two counted
+ * from the source without writing the image -- and from the encoder's own
+ * normalisation and header writer.  No format changes: the estimate only
+ * chooses which existing call to make.
+ *
+ * The estimate is integer arithmetic throughout, so every implementation
+ * gives the same numbers (tests/estimate_ref.py restates it):
+ *
+ *   log2q8(c), 1 <= c <= 32768:  hb = floor(log2 c); x = c << (31 - hb) as a
+ *     u64; y = hb; eight times { x = (x * x) >> 31; y <<= 1; if (x >> 32)
+ *     { x >>= 1; y |= 1; } }; the result y is within 1.01 of 256 * log2 c and
+ *     exact at powers of two.
+ *   cost8(c, L) = 256 * L - log2q8(max(c, 1)): 256 x the bits of a symbol
+ *     whose normalised count is c at table log L; a count of -1 costs L bits.
+ *
+ *   One block, from its byte counts cnt[256], its raw_len and the frame
+ *   parameters nstates, ckpt_interval, table_log (0 = the crate's optimal
+ *   log) and max_table_log:
+ *     RLE, 1 byte, iff cnt[0] == raw_len and raw_len > 0.
+ *     RAW, raw_len bytes, when the encoder status the histogram alone
+ *       determines is not FSE_OK: TOO_SHORT (raw_len < 2), CURSED (a
+ *       histogram Histogram::normalize refuses), or a table log above the
+ *       kernel class of max_table_log (the encoder's UNSUPPORTED).
+ *     Otherwise, with norm[] and L from the encoder's normalisation and hdr
+ *       the exact byte length of NormHistogram::write:
+ *         Q    = sum over s of cnt[s] * cost8(norm[s], L)           (u64)
+ *         bits = ((Q + 255) >> 8) + nstates * L + 1
+ *         comp = hdr + ceil(bits / 8)
+ *         rec  = comp + 8 * fsehip_sidecar_per_block_ns(raw_len, ckpt_interval, nstates)
+ *       and the block is FSE of rec bytes iff rec < raw_len, else RAW.
+ *   A frame: 32 + 4 * n_blocks + the sum of its blocks' bytes.  A plane or
+ *   delta frame: 16 + the frame estimate of its image.
+ *   The choice: the smallest estimate; ties go to the frame, then the plane
+ *   frame, then the delta frame.
+ *
+ * ENCODER_INIT (a block whose coder cannot start, stored RAW) depends on the
+ * order of the bytes, which a histogram does not hold: it is not predicted,
+ * and such a block is estimated as FSE.  The model's error against real
+ * containers is in DESIGN.md section 5 "Estimate" (under 1 % of the length on
+ * the tensors measured there); it is an estimate, never a bound: capacities
+ * stay fsehip_frame_bound and its kin.
+ * ------------------------------------------------------------------------ */
+
+#define FSEHIP_KIND_FRAME 0u  /* section 2b, magic "FSEF" */
+#define FSEHIP_KIND_PLANES 1u /* section 2d, magic "FSEP" */
+#define FSEHIP_KIND_DELTA 2u  /* section 2e, magic "FSED" */
+#define FSEHIP_KIND_SEALED 3u /* section 2f, magic "FSEK": fsehip_container_kind only */
+#define FSEHIP_EST_NONE UINT64_MAX /* an estimate that was not asked for or does not exist */
+#define FSEHIP_EST_RAW 0u /* block types, the frame directory's */
+#define FSEHIP_EST_RLE 1u
+#define FSEHIP_EST_FSE 2u
+
+typedef struct {
+    uint32_t type;      /* FSEHIP_EST_RAW / _RLE / _FSE */
+    uint32_t rec;       /* the record's bytes, checkpoints included */
+    uint32_t bits;      /* payload bits of an FSE block, else 0 */
+    uint32_t table_log; /* of an FSE block, else 0 */
+} fsehip_block_estimate;
+
+/* Host functions, no device.
+ *  fsehip_log2q8: as defined above; 0 for c outside 1..32768.
+ *  fsehip_estimate_choose: the kind of the smallest entry of est[3] (indexed
+ *    by kind) under the tie rule; entries of FSEHIP_EST_NONE do not take
+ *    part, and -1 when all three are (or est is null).
+ *  fsehip_estimate_block_host: the block rule applied to a caller's table:
+ *    counts[256] and raw_len as above; norm[256], norm_log and hdr_bytes the
+ *    normalised counts, their table log and the header length the caller got
+ *    from the normalisation (norm null: the statistics refused the block);
+ *    nstates, ckpt_interval and max_table_log from p.  BAD_ARG for a null
+ *    counts, p or out, nstates above 2, norm_log outside 5..15 or a nonzero
+ *    count whose norm entry is 0 or above 2^norm_log.
+ *  fsehip_container_kind: the FSEHIP_KIND_* value of a buffer's magic (host
+ *    pointer, len = bytes available; a sealed buffer reports
+ *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's),
+ *    FSE_ERR_BAD_FRAME for len < 4 or any other magic, BAD_ARG for a null buf
+ *    with len > 0.  Only the magic is read; the headers have their readers. */
+uint32_t fsehip_log2q8(uint32_t c);
+int fsehip_estimate_choose(const uint64_t est[3]);
+int fsehip_estimate_block_host(const uint32_t counts[256], uint32_t raw_len, const int32_t norm[256],
+                               uint32_t norm_log, uint32_t hdr_bytes, const fsehip_frame_params* p,
+                               fsehip_block_estimate* out);
+int fsehip_container_kind(const uint8_t* buf, size_t len);
+
+/* The bytes a kind's inner frame codes for n_elems elements of elem_bytes:
+ * n_elems * elem_bytes (FRAME), the plane image's (PLANES) or the delta
+ * image's (DELTA).  0 for a kind above 2, elem_bytes outside {1, 2, 4, 8},
+ * PLANES at elem_bytes 1, on overflow, and for n_elems = 0. */
+uint64_t fsehip_estimate_image_bytes(uint32_t kind, uint64_t n_elems, uint32_t elem_bytes);
+
+/* Per-block 256-bin counts of a kind's image: d_counts[b * 256 + s] = how
+ * often byte s occurs in image bytes [b * block_size, (b + 1) * block_size),
+ * for the ceil(fsehip_estimate_image_bytes / block_size) blocks (block_size
+ * 0 = 65536).  FRAME is fsehip_histogram_blocks over the raw bytes; PLANES
+ * (elem_bytes 2, 4, 8) and DELTA (1, 2, 4, 8) read the source once and write
+ * no image: the zero pads up to the stride are counted, and blocks that
+ * straddle two planes hold bytes of both, exactly as the image's blocks do.
+ * d_src aligned to elem_bytes (reads go up to roundup(n_elems * elem_bytes,
+ * 4) at most), d_counts to 4.  Asynchronous on `stream`, no host
+ * synchronisation, no workspace.  Before any device use: BAD_ARG (kind above
+ * 2, a null or misaligned pointer with n_elems > 0, more than one block of a
+ * size that is no multiple of 16, more than 2^32 - 1 blocks), UNSUPPORTED
+ * (elem_bytes outside {1, 2, 4, 8}, PLANES at elem_bytes 1, a size
+ * overflowing), NO_DEVICE.  n_elems == 0 returns FSE_OK and does nothing. */
+int fsehip_image_histogram(uint32_t kind, uint32_t elem_bytes, const void* d_src, uint64_t n_elems,
+                           uint32_t block_size, uint32_t* d_counts, fsehip_stream_t stream);
+
+/* The block rule on the device, one wave per block, with the encoder's own
+ * optimal_log2 / normalize / header writer: d_counts as
+ * fsehip_image_histogram gives them (or a caller's, 256 per block, each
+ * block's summing to its raw length) for an image of n_image_bytes in blocks
+ * of p->block_size.  Per block b, each output optional (null: not written):
+ * d_type[b] (u8, FSEHIP_EST_*), d_rec[b], d_bits[b] and d_log[b] (u8) as in
+ * fsehip_block_estimate.  *d_total (required) = 32 + 4 * n_blocks + the sum
+ * of rec: the frame estimate.  p's table_log, ckpt_interval, max_table_log
+ * and nstates mean what they mean to fsehip_frame_compress; chunk_blocks is
+ * not used.  Asynchronous on `stream`, no host synchronisation, no workspace.
+ * Before any device use: BAD_ARG (a null p, d_total, or d_counts with
+ * n_image_bytes > 0; d_counts, d_rec, d_bits not 4-byte or d_total not 8-byte
+ * aligned; nstates above 2; a checkpoint interval fsehip_frame_compress
+ * refuses; the block rules of fsehip_frame_compress), UNSUPPORTED (a block
+ * size above 2^28), NO_DEVICE. */
+int fsehip_estimate_blocks(const fsehip_frame_params* p, const uint32_t* d_counts, uint64_t n_image_bytes,
+                           uint8_t* d_type, uint32_t* d_rec, uint32_t* d_bits, uint8_t* d_log, uint64_t* d_total,
+                           fsehip_stream_t stream);
+
+/* The scratch of fsehip_estimate: the counts of the largest image among the
+ * kinds of kind_mask (bit k = kind k) that take elem_bytes, 1024 bytes per
+ * block; the kinds run one after the other on it.  0 for a kind_mask of 0 or
+ * above 7, elem_bytes outside {1, 2, 4, 8}, on overflow, and when nothing is
+ * needed (n_elems = 0). */
+uint64_t fsehip_estimate_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes, uint32_t kind_mask,
+                                       uint32_t block_size);
+
+/* The estimated length of each container of kind_mask for the n_elems
+ * elements of elem_bytes at d_src, under the frame parameters p: d_est[k]
+ * (device, three u64) = the estimate of kind k, or FSEHIP_EST_NONE when bit k
+ * of kind_mask is clear or the kind does not take the width (PLANES at
+ * elem_bytes 1).  Per kind: the counts zeroed, fsehip_image_histogram,
+ * fsehip_estimate_blocks, all on `stream` with no host synchronisation; the
+ * caller reads d_est when the stream gets there and calls
+ * fsehip_estimate_choose.  d_scratch: fsehip_estimate_scratch_bytes, 16-byte
+ * aligned; nothing is allocated and no workspace is held.  n_elems = 0 gives
+ * the empty containers' lengths (32, 48, 48).  Before any device use: BAD_ARG
+ * (a null p or d_est, kind_mask 0 or above 7, a null d_src or d_scratch with
+ * n_elems > 0, d_src not aligned to elem_bytes, d_scratch to 16 or d_est to
+ * 8, and fsehip_estimate_blocks' rules for p on every image), UNSUPPORTED
+ * (elem_bytes outside {1, 2, 4, 8}, a size overflowing, a block size above
+ * 2^28), DST_TOO_SMALL (scratch_bytes below fsehip_estimate_scratch_bytes),
+ * NO_DEVICE. */
+int fsehip_estimate(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t elem_bytes, const void* d_src,
+                    uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes, uint64_t* d_est,
+                    fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
  *
  * The crate's `pub mod fse` lets a caller code any number of messages against
