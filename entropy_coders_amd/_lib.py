@@ -111,7 +111,7 @@ class FrameParams(C.Structure):
 
 
 class PlanesInfo(C.Structure):
-    """fsehip_planes_info: a plane frame's header fields, stride = roundup(n_elems, 16)."""
+    """fsehip_planes_info: a plane or delta frame's header fields, stride = roundup(n_elems, 16)."""
     _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
                 ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
 
@@ -124,10 +124,7 @@ class PlanesRange(C.Structure):
 DELTA_RESTART = 4096  # FSEHIP_DELTA_RESTART: elements between the delta frame's restarts
 
 
-class DeltaInfo(C.Structure):
-    """fsehip_delta_info: a delta frame's header fields, stride = roundup(n_elems, 16)."""
-    _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
-                ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
+DeltaInfo = PlanesInfo  # fsehip_delta_info is a typedef of fsehip_planes_info
 
 
 CHECK_CRC32 = 1  # FSEHIP_CHECK_CRC32: the check record's algorithm
@@ -262,36 +259,24 @@ def load() -> C.CDLL:
     lib.fsehip_frame_decompress_ranges.argtypes = [C.POINTER(FrameInfo), u32, P, u64, C.POINTER(FrameRange), u32, P, u64,
                                                    P, P, P]
     lib.fsehip_frame_decompress_range.argtypes = [C.POINTER(FrameInfo), u32, P, u64, u64, u64, P, u64, P, P]
-    PI, FI = C.POINTER(PlanesInfo), C.POINTER(FrameInfo)
-    lib.fsehip_planes_bound.argtypes = [u64, u32, u32]
-    lib.fsehip_planes_bound.restype = u64
-    lib.fsehip_planes_scratch_bytes.argtypes = [u64, u32]
-    lib.fsehip_planes_scratch_bytes.restype = u64
-    lib.fsehip_planes_read_header.argtypes = [P, sz, PI, FI]
-    lib.fsehip_planes_write_header.argtypes = [PI, P]
-    lib.fsehip_planes_split.argtypes = [u32, P, u64, P, P]
-    lib.fsehip_planes_merge.argtypes = [u32, P, u64, P, P]
-    lib.fsehip_planes_compress.argtypes = [C.POINTER(FrameParams), u32, P, u64, P, u64, P, u64, P, P, P]
-    lib.fsehip_planes_decompress.argtypes = [PI, FI, u32, P, u64, P, u64, P, u64, P, P, P]
-    lib.fsehip_planes_ranges_scratch_bytes.argtypes = [u32, C.POINTER(PlanesRange), u32]
-    lib.fsehip_planes_ranges_scratch_bytes.restype = u64
-    lib.fsehip_planes_decompress_ranges.argtypes = [PI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
-                                                    P, P, P]
-    DI = C.POINTER(DeltaInfo)
-    lib.fsehip_delta_bound.argtypes = [u64, u32, u32]
-    lib.fsehip_delta_bound.restype = u64
-    lib.fsehip_delta_scratch_bytes.argtypes = [u64, u32]
-    lib.fsehip_delta_scratch_bytes.restype = u64
-    lib.fsehip_delta_read_header.argtypes = [P, sz, DI, FI]
-    lib.fsehip_delta_write_header.argtypes = [DI, P]
-    lib.fsehip_delta_encode.argtypes = [u32, P, u64, P, P]
-    lib.fsehip_delta_decode.argtypes = [u32, P, u64, P, P]
-    lib.fsehip_delta_compress.argtypes = [C.POINTER(FrameParams), u32, P, u64, P, u64, P, u64, P, P, P]
-    lib.fsehip_delta_decompress.argtypes = [DI, FI, u32, P, u64, P, u64, P, u64, P, P, P]
-    lib.fsehip_delta_ranges_scratch_bytes.argtypes = [u32, C.POINTER(PlanesRange), u32]
-    lib.fsehip_delta_ranges_scratch_bytes.restype = u64
-    lib.fsehip_delta_decompress_ranges.argtypes = [DI, FI, u32, P, u64, C.POINTER(PlanesRange), u32, P, u64, P, u64,
-                                                   P, P, P]
+    # the plane and the delta frame: the same ten prototypes under two
+    # prefixes, but for the names of the two bare transforms
+    PI, FI, PR = C.POINTER(PlanesInfo), C.POINTER(FrameInfo), C.POINTER(PlanesRange)
+    for prefix, split, merge in (("fsehip_planes_", "split", "merge"), ("fsehip_delta_", "encode", "decode")):
+        fn = lambda name, prefix=prefix: getattr(lib, prefix + name)  # noqa: E731
+        fn("bound").argtypes = [u64, u32, u32]
+        fn("bound").restype = u64
+        fn("scratch_bytes").argtypes = [u64, u32]
+        fn("scratch_bytes").restype = u64
+        fn("read_header").argtypes = [P, sz, PI, FI]
+        fn("write_header").argtypes = [PI, P]
+        fn(split).argtypes = [u32, P, u64, P, P]
+        fn(merge).argtypes = [u32, P, u64, P, P]
+        fn("compress").argtypes = [C.POINTER(FrameParams), u32, P, u64, P, u64, P, u64, P, P, P]
+        fn("decompress").argtypes = [PI, FI, u32, P, u64, P, u64, P, u64, P, P, P]
+        fn("ranges_scratch_bytes").argtypes = [u32, PR, u32]
+        fn("ranges_scratch_bytes").restype = u64
+        fn("decompress_ranges").argtypes = [PI, FI, u32, P, u64, PR, u32, P, u64, P, u64, P, P, P]
     CI = C.POINTER(CheckInfo)
     lib.fsehip_crc32.argtypes = [u32, P, sz]
     lib.fsehip_crc32.restype = u32

@@ -1,7 +1,7 @@
 // fse_check.cpp -- the check record's header, sizes, CRC-32 and range planner,
 // host side (fsehip.h section 2f).
 //
-// Plain C++ with no HIP include, as fse_planes.cpp: the same source builds
+// Plain C++ with no HIP include, as fse_elem.cpp: the same source builds
 // into libfsehip.so and, with g++ alone, into the sanitizer fuzz of
 // tests/native/check_fuzz.cpp.  The kernels are fse_check.hip, the device
 // calls fse_capi_check.cpp; their tables and constants come from

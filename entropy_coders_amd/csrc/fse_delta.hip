@@ -20,8 +20,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "fse_delta_host.h"
 #include "fse_device.hpp"
+#include "fse_elem_host.h"
 #include "fse_planes_dev.hpp"
 
 namespace fsehip {

@@ -2,7 +2,7 @@
 // the integer cost model applied to a caller's table, the choice, the sizes
 // and the container's kind from its magic.
 //
-// Plain C++ with no HIP include, as fse_delta.cpp: the same source builds
+// Plain C++ with no HIP include, as fse_elem.cpp: the same source builds
 // into libfsehip.so and, with g++ alone, into the sanitizer fuzz of
 // tests/native/estimate_fuzz.cpp.  The kernels are fse_estimate.hip, the
 // device calls fse_capi_estimate.cpp.

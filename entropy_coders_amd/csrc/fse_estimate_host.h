@@ -2,7 +2,7 @@
 // (fsehip.h section 2g): the integer cost model of fse_estimate.cpp, written
 // once for the host and the device, and the launchers of fse_estimate.hip,
 // called by fse_capi_estimate.cpp.  Plain C++ with no HIP include (a stream
-// travels as void*), as fse_delta_host.h.  Not part of the public ABI.
+// travels as void*), as fse_elem_host.h.  Not part of the public ABI.
 #pragma once
 #include <stdint.h>
 

@@ -17,7 +17,7 @@
 #include <stdint.h>
 
 #include "fse_planes_dev.hpp"
-#include "fse_planes_host.h"
+#include "fse_elem_host.h"
 
 namespace fsehip {
 
@@ -213,15 +213,15 @@ int launch_planes_pieces(uint32_t w, const uint8_t* scratch, const PlanePieces& 
     return done();
 }
 
-int launch_planes_finish(const uint8_t hdr[16], uint8_t* out, uint64_t* out_len, void* stream) {
+int launch_elem_finish(const uint8_t hdr[16], uint8_t* out, uint64_t* out_len, void* stream) {
     Hdr16 h;
     for (int i = 0; i < 16; ++i) h.b[i] = hdr[i];
     hipLaunchKernelGGL(planes_finish_kernel, dim3(1), dim3(64), 0, static_cast<hipStream_t>(stream), h, out, out_len);
     return done();
 }
 
-int launch_planes_check(const uint8_t hdr[16], const uint8_t* in, int32_t* result, int32_t* status,
-                        uint64_t n_status, bool zero_count, void* stream) {
+int launch_elem_check(const uint8_t hdr[16], const uint8_t* in, int32_t* result, int32_t* status,
+                      uint64_t n_status, bool zero_count, void* stream) {
     Hdr16 h;
     for (int i = 0; i < 16; ++i) h.b[i] = hdr[i];
     hipLaunchKernelGGL(planes_check_kernel, dim3(status ? grid_for(n_status ? n_status : 1u) : 1u), dim3(PL_T), 0,
@@ -229,8 +229,8 @@ int launch_planes_check(const uint8_t hdr[16], const uint8_t* in, int32_t* resul
     return done();
 }
 
-int launch_planes_range_status(uint32_t w, const int32_t* plane_status, uint32_t n_ranges, int32_t* range_status,
-                               int32_t* result, void* stream) {
+int launch_elem_range_status(uint32_t w, const int32_t* plane_status, uint32_t n_ranges, int32_t* range_status,
+                             int32_t* result, void* stream) {
     if (n_ranges == 0) return FSE_OK;
     hipLaunchKernelGGL(planes_range_status_kernel, dim3(grid_for(n_ranges)), dim3(PL_T), 0,
                        static_cast<hipStream_t>(stream), w, plane_status, n_ranges, range_status, result);

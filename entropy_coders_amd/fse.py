@@ -26,6 +26,20 @@ def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
 
 
+class _ElemKind:
+    """What tells the two element frames (fsehip.h sections 2d, 2e) apart:
+    the C names' prefix and their names of the two bare transforms, the
+    element widths taken, the info class and the label used in messages."""
+
+    def __init__(self, prefix: str, split: str, merge: str, widths: tuple, info, label: str):
+        self.prefix, self.split, self.merge = prefix, split, merge
+        self.widths, self.info, self.label = widths, info, label
+        self.takes = ", ".join(map(str, widths[:-1])) + f" or {widths[-1]}"  # "2, 4 or 8"
+
+
+_ELEM = {"planes": _ElemKind("fsehip_planes_", "split", "merge", (2, 4, 8), PlanesInfo, "plane"),
+         "delta": _ElemKind("fsehip_delta_", "encode", "decode", (1, 2, 4, 8), DeltaInfo, "delta")}
+
 _tls = threading.local()
 
 
@@ -774,82 +788,91 @@ class BlockCodec:
         check(int(status[0].item()), "frame range")
         return views[0]
 
-    # ------------------------------------------------------------ the plane frame
-    # fsehip.h section 2d: byte k of every element into plane k, the planes
-    # coded by one frame.  The container stores the element width; dtype and
-    # shape stay with the caller.
+    # ------------------------------------------------------------ the element frames
+    # fsehip.h sections 2d and 2e: one container under two names.  The plane
+    # frame puts byte k of every element into plane k and codes the planes by
+    # one frame.  The delta frame first takes the zigzag differences of
+    # neighbouring elements, with a restart every 4,096: for integer tensors
+    # that grow (sorted ids, offsets, timestamps); any dtype of 1, 2, 4 or 8
+    # bytes round-trips, floats gain nothing.  The container stores the element
+    # width; dtype and shape stay with the caller.  The `_elem_*` methods take
+    # the kind, "planes" or "delta" (a row of _ELEM); the public names forward.
+    def _elem_fn(self, kind: str, name: str):
+        return getattr(self.lib, _ELEM[kind].prefix + name)
+
+    def _elem_call(self, kind: str, name: str, *args) -> None:
+        check(self._elem_fn(kind, name)(*args), _ELEM[kind].prefix + name)
+
     @staticmethod
-    def _elem_bytes(x) -> int:
-        w = x.element_size()
-        if w == 1:
-            raise ValueError("compress_planes is for 2-, 4- and 8-byte elements; 1-byte tensors go to compress_frame")
-        if w not in (2, 4, 8):
-            raise ValueError(f"element size {w}: the plane frame takes 2, 4 or 8 bytes")
+    def _elem_width(kind: str, x) -> int:
+        k, w = _ELEM[kind], x.element_size()
+        if w == 1 and 1 not in k.widths:  # the plane frame
+            raise ValueError(f"compress_{kind} is for 2-, 4- and 8-byte elements; 1-byte tensors go to compress_frame")
+        if w not in k.widths:
+            raise ValueError(f"element size {w}: the {k.label} frame takes {k.takes} bytes")
         if not x.is_contiguous():
-            raise ValueError("compress_planes needs a contiguous tensor")
+            raise ValueError(f"compress_{kind} needs a contiguous tensor")
         return w
 
-    def planes_bound(self, n_elems: int, elem_bytes: int) -> int:
-        """`fsehip_planes_bound`: a capacity no plane frame of n_elems elements exceeds."""
-        return int(self.lib.fsehip_planes_bound(n_elems, elem_bytes, self.block_size))
+    def _elem_bound(self, kind: str, n_elems: int, elem_bytes: int) -> int:
+        return int(self._elem_fn(kind, "bound")(n_elems, elem_bytes, self.block_size))
 
-    def planes_scratch_bytes(self, n_elems: int, elem_bytes: int) -> int:
-        """`fsehip_planes_scratch_bytes`: the plane image's bytes."""
-        return int(self.lib.fsehip_planes_scratch_bytes(n_elems, elem_bytes))
+    def _elem_scratch_bytes(self, kind: str, n_elems: int, elem_bytes: int) -> int:
+        return int(self._elem_fn(kind, "scratch_bytes")(n_elems, elem_bytes))
 
-    def planes_split(self, x):
-        """`fsehip_planes_split`: the plane image of a contiguous device tensor (uint8, pads zeroed)."""
-        w = self._elem_bytes(x)
-        image = self.torch.empty(self.planes_scratch_bytes(x.numel(), w), dtype=self.torch.uint8, device=self.device)
-        check(self.lib.fsehip_planes_split(w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(image.data_ptr()),
-                                           self._stream()), "fsehip_planes_split")
+    def _elem_split(self, kind: str, x):
+        """The image of a contiguous device tensor (uint8, pads zeroed)."""
+        w = self._elem_width(kind, x)
+        image = self.torch.empty(self._elem_scratch_bytes(kind, x.numel(), w), dtype=self.torch.uint8,
+                                 device=self.device)
+        self._elem_call(kind, _ELEM[kind].split, w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(image.data_ptr()),
+                        self._stream())
         return image
 
-    def planes_merge(self, image, n_elems: int, dtype):
-        """`fsehip_planes_merge`: n_elems elements of `dtype` from a plane image."""
+    def _elem_merge(self, kind: str, image, n_elems: int, dtype):
+        """n_elems elements of `dtype` from an image."""
         out = self.torch.empty(n_elems, dtype=dtype, device=self.device)
-        check(self.lib.fsehip_planes_merge(out.element_size(), C.c_void_p(image.data_ptr()), n_elems,
-                                           C.c_void_p(out.data_ptr()), self._stream()), "fsehip_planes_merge")
+        self._elem_call(kind, _ELEM[kind].merge, out.element_size(), C.c_void_p(image.data_ptr()), n_elems,
+                        C.c_void_p(out.data_ptr()), self._stream())
         return out
 
-    def compress_planes_into(self, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
-        """`fsehip_planes_compress`, no synchronisation: `scratch` a uint8
-        device tensor of >= planes_scratch_bytes, `out` of >= planes_bound
-        bytes (any alignment), `out_len` one int64, `result` two int32."""
-        w = self._elem_bytes(x)
-        p = FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
-                        chunk_blocks)
-        check(self.lib.fsehip_planes_compress(
-            C.byref(p), w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(),
-            C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()),
-            self._stream()), "fsehip_planes_compress")
+    def _elem_compress_into(self, kind: str, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+        """The compress call, no synchronisation: `scratch` a uint8 device
+        tensor of >= the kind's scratch_bytes, `out` of >= its bound bytes (any
+        alignment), `out_len` one int64, `result` two int32."""
+        w = self._elem_width(kind, x)
+        p = self._frame_params(chunk_blocks)
+        self._elem_call(kind, "compress", C.byref(p), w, C.c_void_p(x.data_ptr()), x.numel(),
+                        C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()), out.numel(),
+                        C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()), self._stream())
 
-    def compress_planes(self, x, chunk_blocks: int = 0):
-        """Compress a contiguous device tensor of 2-, 4- or 8-byte elements
-        into one plane frame: a uint8 device tensor of its exact length.  One
-        synchronisation, to read the length."""
+    def _elem_compress(self, kind: str, x, chunk_blocks: int = 0):
+        """Compress a contiguous device tensor of one of the kind's element
+        widths into one frame of the kind: a uint8 device tensor of its exact
+        length.  One synchronisation, to read the length."""
         t = self.torch
-        w = self._elem_bytes(x)
-        scratch = t.empty(self.planes_scratch_bytes(x.numel(), w), dtype=t.uint8, device=self.device)
-        out = t.empty(self.planes_bound(x.numel(), w), dtype=t.uint8, device=self.device)
+        w = self._elem_width(kind, x)
+        scratch = t.empty(self._elem_scratch_bytes(kind, x.numel(), w), dtype=t.uint8, device=self.device)
+        out = t.empty(self._elem_bound(kind, x.numel(), w), dtype=t.uint8, device=self.device)
         out_len = t.zeros(1, dtype=t.int64, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.compress_planes_into(x, scratch, out, out_len, result, chunk_blocks)
+        self._elem_compress_into(kind, x, scratch, out, out_len, result, chunk_blocks)
         return out[: int(out_len.item())]
 
     @staticmethod
-    def planes_info(buf):
-        """`fsehip_planes_read_header` of a plane frame given as bytes, a numpy
-        array or a tensor (its first 48 bytes come to the host): (PlanesInfo,
-        the inner frame's FrameInfo); raises FseError (BAD_FRAME) otherwise."""
+    def _elem_info(kind: str, buf):
+        """The read-header call of a frame of the kind given as bytes, a numpy
+        array or a tensor (its first 48 bytes come to the host): (the kind's
+        info, the inner frame's FrameInfo); raises FseError (BAD_FRAME)
+        otherwise."""
         if hasattr(buf, "data_ptr"):  # a torch tensor
             head = buf[:48].cpu().numpy().tobytes()
         else:
             head = bytes(memoryview(buf)[:48])
         a = np.frombuffer(head, dtype=np.uint8)
-        info, inner = PlanesInfo(), FrameInfo()
-        check(load().fsehip_planes_read_header(_p(a), len(a), C.byref(info), C.byref(inner)),
-              "fsehip_planes_read_header")
+        info, inner = _ELEM[kind].info(), FrameInfo()
+        name = _ELEM[kind].prefix + "read_header"
+        check(getattr(load(), name)(_p(a), len(a), C.byref(info), C.byref(inner)), name)
         return info, inner
 
     def _check_dtype(self, info, dtype, kind: str = "plane") -> None:
@@ -857,251 +880,205 @@ class BlockCodec:
         if w != info.elem_bytes:
             raise ValueError(f"dtype {dtype} has {w}-byte elements, the {kind} frame holds {info.elem_bytes}-byte ones")
 
-    def decompress_planes_into(self, buf, info: PlanesInfo, inner: FrameInfo, scratch, out, block_status, result,
-                               chunk_blocks: int = 0) -> None:
-        """`fsehip_planes_decompress`, no synchronisation: `scratch` >=
-        inner.n_total bytes, `out` info.n_elems elements (16-byte aligned),
-        `block_status` inner.n_blocks int32 or None, `result` two int32."""
-        check(self.lib.fsehip_planes_decompress(
-            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
-            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
-            out.numel() * out.element_size(),
-            C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
-            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_planes_decompress")
+    def _elem_decompress_into(self, kind: str, buf, info, inner: FrameInfo, scratch, out, block_status, result,
+                              chunk_blocks: int = 0) -> None:
+        """The decompress call, no synchronisation: `scratch` >= inner.n_total
+        bytes, `out` info.n_elems elements (16-byte aligned), `block_status`
+        inner.n_blocks int32 or None, `result` two int32."""
+        self._elem_call(kind, "decompress", C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()),
+                        buf.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
+                        out.numel() * out.element_size(),
+                        C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
+                        C.c_void_p(result.data_ptr()), self._stream())
 
-    def decompress_planes(self, buf, dtype, chunk_blocks: int = 0):
-        """Decode a plane frame (a uint8 device tensor) into a 1-D tensor of
-        `dtype`, whose size must be the frame's element width (ValueError
-        otherwise).  Returns (out, block_status); raises FseError for a
-        frame-level error (BAD_FRAME)."""
+    def _elem_decompress(self, kind: str, buf, dtype, chunk_blocks: int = 0):
+        """Decode a frame of the kind (a uint8 device tensor) into a 1-D
+        tensor of `dtype`, whose size must be the frame's element width
+        (ValueError otherwise).  Returns (out, block_status); raises FseError
+        for a frame-level error (BAD_FRAME)."""
         t = self.torch
-        info, inner = self.planes_info(buf)
-        self._check_dtype(info, dtype)
+        info, inner = self._elem_info(kind, buf)
+        self._check_dtype(info, dtype, _ELEM[kind].label)
         scratch = t.empty(inner.n_total, dtype=t.uint8, device=self.device)
         out = t.empty(info.n_elems, dtype=dtype, device=self.device)
         status = t.zeros(inner.n_blocks, dtype=t.int32, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_planes_into(buf, info, inner, scratch, out, status, result, chunk_blocks)
-        check(int(result[0].item()), "plane frame")
+        self._elem_decompress_into(kind, buf, info, inner, scratch, out, status, result, chunk_blocks)
+        check(int(result[0].item()), f"{_ELEM[kind].label} frame")
         return out, status
 
     @staticmethod
     def planes_ranges(ranges):
-        """(elem_off, n_elems, dst_elem_off) triples as the fsehip_planes_range array the C call reads."""
+        """(elem_off, n_elems, dst_elem_off) triples as the fsehip_planes_range array the C calls of both kinds read."""
         arr = (PlanesRange * max(len(ranges), 1))(*[PlanesRange(int(s), int(n), int(d)) for s, n, d in ranges])
         arr.empty = len(ranges) == 0
         return arr
 
-    def planes_ranges_scratch_bytes(self, elem_bytes: int, ranges) -> int:
-        """`fsehip_planes_ranges_scratch_bytes` for a sequence of triples or a `planes_ranges` array."""
+    def _elem_ranges_scratch_bytes(self, kind: str, elem_bytes: int, ranges) -> int:
         arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
         n = 0 if getattr(arr, "empty", False) else len(arr)
-        return int(self.lib.fsehip_planes_ranges_scratch_bytes(elem_bytes, arr, n))
+        return int(self._elem_fn(kind, "ranges_scratch_bytes")(elem_bytes, arr, n))
+
+    def _elem_decompress_ranges_into(self, kind: str, buf, info, inner: FrameInfo, ranges, scratch, out, range_status,
+                                     result, chunk_blocks: int = 0) -> None:
+        """The decompress-ranges call, no synchronisation: `ranges` a sequence
+        of (elem_off, n_elems, dst_elem_off) or what `planes_ranges` made of
+        one; `scratch` >= the kind's ranges_scratch_bytes; range r goes to
+        out[dst_elem_off: dst_elem_off + n_elems] (`out` of the frame's
+        element width, any alignment)."""
+        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
+        n = 0 if getattr(arr, "empty", False) else len(arr)
+        self._elem_call(kind, "decompress_ranges", C.byref(info), C.byref(inner), chunk_blocks,
+                        C.c_void_p(buf.data_ptr()), buf.numel(), arr, n, C.c_void_p(scratch.data_ptr()),
+                        scratch.numel(), C.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                        C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
+                        C.c_void_p(result.data_ptr()), self._stream())
+
+    def _elem_decompress_ranges(self, kind: str, buf, dtype, ranges, chunk_blocks: int = 0):
+        """Decode the element ranges [(elem_off, count), ...] of a frame of the
+        kind without decoding the rest (a delta range from its restart group's
+        first element on).  The ranges are packed back to back into one
+        tensor of `dtype`; returns (list of views of it, one per range, and
+        the int32 range statuses).  Raises FseError for a frame-level error
+        (BAD_FRAME)."""
+        t = self.torch
+        info, inner = self._elem_info(kind, buf)
+        self._check_dtype(info, dtype, _ELEM[kind].label)
+        packed, at = [], 0
+        for s, n in ranges:
+            packed.append((s, n, at))
+            at += n
+        arr = self.planes_ranges(packed)
+        scratch = t.empty(max(self._elem_ranges_scratch_bytes(kind, info.elem_bytes, arr), 16), dtype=t.uint8,
+                          device=self.device)
+        out = t.empty(at, dtype=dtype, device=self.device)
+        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self._elem_decompress_ranges_into(kind, buf, info, inner, arr, scratch, out, status, result, chunk_blocks)
+        check(int(result[0].item()), f"{_ELEM[kind].label} frame")
+        return [out[d: d + n] for _, n, d in packed], status
+
+    def _elem_decompress_range(self, kind: str, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0):
+        """Elements [elem_off, elem_off + count) of a frame of the kind as a
+        tensor of `dtype`; raises FseError for a frame-level error or with the
+        status of the first failed block the range needs."""
+        views, status = self._elem_decompress_ranges(kind, buf, dtype, [(elem_off, count)], chunk_blocks)
+        check(int(status[0].item()), f"{_ELEM[kind].label} frame range")
+        return views[0]
+
+    # the plane frame's names (2-, 4- and 8-byte elements)
+    def planes_bound(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_planes_bound`: a capacity no plane frame of n_elems elements exceeds."""
+        return self._elem_bound("planes", n_elems, elem_bytes)
+
+    def planes_scratch_bytes(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_planes_scratch_bytes`: the plane image's bytes."""
+        return self._elem_scratch_bytes("planes", n_elems, elem_bytes)
+
+    def planes_split(self, x):
+        """`fsehip_planes_split`: `_elem_split` for the plane image."""
+        return self._elem_split("planes", x)
+
+    def planes_merge(self, image, n_elems: int, dtype):
+        """`fsehip_planes_merge`: `_elem_merge` from a plane image."""
+        return self._elem_merge("planes", image, n_elems, dtype)
+
+    def compress_planes_into(self, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_planes_compress`: `_elem_compress_into` for a plane frame."""
+        self._elem_compress_into("planes", x, scratch, out, out_len, result, chunk_blocks)
+
+    def compress_planes(self, x, chunk_blocks: int = 0):
+        """`_elem_compress` into one plane frame."""
+        return self._elem_compress("planes", x, chunk_blocks)
+
+    @staticmethod
+    def planes_info(buf):
+        """`fsehip_planes_read_header`: `_elem_info`, (PlanesInfo, FrameInfo)."""
+        return BlockCodec._elem_info("planes", buf)
+
+    def decompress_planes_into(self, buf, info: PlanesInfo, inner: FrameInfo, scratch, out, block_status, result,
+                               chunk_blocks: int = 0) -> None:
+        """`fsehip_planes_decompress`: `_elem_decompress_into` for a plane frame."""
+        self._elem_decompress_into("planes", buf, info, inner, scratch, out, block_status, result, chunk_blocks)
+
+    def decompress_planes(self, buf, dtype, chunk_blocks: int = 0):
+        """`_elem_decompress` of a plane frame: (out, block_status)."""
+        return self._elem_decompress("planes", buf, dtype, chunk_blocks)
+
+    def planes_ranges_scratch_bytes(self, elem_bytes: int, ranges) -> int:
+        """`fsehip_planes_ranges_scratch_bytes` for a sequence of triples or a `planes_ranges` array."""
+        return self._elem_ranges_scratch_bytes("planes", elem_bytes, ranges)
 
     def decompress_planes_ranges_into(self, buf, info: PlanesInfo, inner: FrameInfo, ranges, scratch, out,
                                       range_status, result, chunk_blocks: int = 0) -> None:
-        """`fsehip_planes_decompress_ranges`, no synchronisation: `ranges` a
-        sequence of (elem_off, n_elems, dst_elem_off) or what `planes_ranges`
-        made of one; `scratch` >= planes_ranges_scratch_bytes; range r goes
-        to out[dst_elem_off: dst_elem_off + n_elems] (`out` of the frame's
-        element width, any alignment)."""
-        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
-        n = 0 if getattr(arr, "empty", False) else len(arr)
-        check(self.lib.fsehip_planes_decompress_ranges(
-            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(), arr, n,
-            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
-            out.numel() * out.element_size(),
-            C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
-            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_planes_decompress_ranges")
+        """`fsehip_planes_decompress_ranges`: `_elem_decompress_ranges_into` for a plane frame."""
+        self._elem_decompress_ranges_into("planes", buf, info, inner, ranges, scratch, out, range_status, result,
+                                          chunk_blocks)
 
     def decompress_planes_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0):
-        """Decode the element ranges [(elem_off, count), ...] of a plane frame
-        without decoding the rest.  The ranges are packed back to back into
-        one tensor of `dtype`; returns (list of views of it, one per range,
-        and the int32 range statuses).  Raises FseError for a frame-level
-        error (BAD_FRAME)."""
-        t = self.torch
-        info, inner = self.planes_info(buf)
-        self._check_dtype(info, dtype)
-        packed, at = [], 0
-        for s, n in ranges:
-            packed.append((s, n, at))
-            at += n
-        arr = self.planes_ranges(packed)
-        scratch = t.empty(max(self.planes_ranges_scratch_bytes(info.elem_bytes, arr), 16), dtype=t.uint8,
-                          device=self.device)
-        out = t.empty(at, dtype=dtype, device=self.device)
-        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
-        result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_planes_ranges_into(buf, info, inner, arr, scratch, out, status, result, chunk_blocks)
-        check(int(result[0].item()), "plane frame")
-        return [out[d: d + n] for _, n, d in packed], status
+        """`_elem_decompress_ranges` of a plane frame: (views, range statuses)."""
+        return self._elem_decompress_ranges("planes", buf, dtype, ranges, chunk_blocks)
 
     def decompress_planes_range(self, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0):
-        """Elements [elem_off, elem_off + count) of a plane frame as a tensor
-        of `dtype`; raises FseError for a frame-level error or with the
-        status of the first failed block the range touches."""
-        views, status = self.decompress_planes_ranges(buf, dtype, [(elem_off, count)], chunk_blocks)
-        check(int(status[0].item()), "plane frame range")
-        return views[0]
+        """`_elem_decompress_range` of a plane frame: one tensor."""
+        return self._elem_decompress_range("planes", buf, dtype, elem_off, count, chunk_blocks)
 
-    # ------------------------------------------------------------ the delta frame
-    # fsehip.h section 2e: zigzag differences of neighbouring elements with a
-    # restart every 4,096, split into byte planes and coded by one frame.  For
-    # integer tensors that grow (sorted ids, offsets, timestamps); any dtype
-    # of 1, 2, 4 or 8 bytes round-trips, floats gain nothing.
-    @staticmethod
-    def _delta_elem_bytes(x) -> int:
-        w = x.element_size()
-        if w not in (1, 2, 4, 8):
-            raise ValueError(f"element size {w}: the delta frame takes 1, 2, 4 or 8 bytes")
-        if not x.is_contiguous():
-            raise ValueError("compress_delta needs a contiguous tensor")
-        return w
-
+    # the delta frame's names (1-, 2-, 4- and 8-byte elements)
     def delta_bound(self, n_elems: int, elem_bytes: int) -> int:
         """`fsehip_delta_bound`: a capacity no delta frame of n_elems elements exceeds."""
-        return int(self.lib.fsehip_delta_bound(n_elems, elem_bytes, self.block_size))
+        return self._elem_bound("delta", n_elems, elem_bytes)
 
     def delta_scratch_bytes(self, n_elems: int, elem_bytes: int) -> int:
         """`fsehip_delta_scratch_bytes`: the delta image's bytes."""
-        return int(self.lib.fsehip_delta_scratch_bytes(n_elems, elem_bytes))
+        return self._elem_scratch_bytes("delta", n_elems, elem_bytes)
 
     def delta_encode(self, x):
-        """`fsehip_delta_encode`: the delta image of a contiguous device tensor (uint8, pads zeroed)."""
-        w = self._delta_elem_bytes(x)
-        image = self.torch.empty(self.delta_scratch_bytes(x.numel(), w), dtype=self.torch.uint8, device=self.device)
-        check(self.lib.fsehip_delta_encode(w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(image.data_ptr()),
-                                           self._stream()), "fsehip_delta_encode")
-        return image
+        """`fsehip_delta_encode`: `_elem_split` for the delta image."""
+        return self._elem_split("delta", x)
 
     def delta_decode(self, image, n_elems: int, dtype):
-        """`fsehip_delta_decode`: n_elems elements of `dtype` from a delta image."""
-        out = self.torch.empty(n_elems, dtype=dtype, device=self.device)
-        check(self.lib.fsehip_delta_decode(out.element_size(), C.c_void_p(image.data_ptr()), n_elems,
-                                           C.c_void_p(out.data_ptr()), self._stream()), "fsehip_delta_decode")
-        return out
+        """`fsehip_delta_decode`: `_elem_merge` from a delta image."""
+        return self._elem_merge("delta", image, n_elems, dtype)
 
     def compress_delta_into(self, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
-        """`fsehip_delta_compress`, no synchronisation: `scratch` a uint8
-        device tensor of >= delta_scratch_bytes, `out` of >= delta_bound
-        bytes (any alignment), `out_len` one int64, `result` two int32."""
-        w = self._delta_elem_bytes(x)
-        p = FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
-                        chunk_blocks)
-        check(self.lib.fsehip_delta_compress(
-            C.byref(p), w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(),
-            C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()),
-            self._stream()), "fsehip_delta_compress")
+        """`fsehip_delta_compress`: `_elem_compress_into` for a delta frame."""
+        self._elem_compress_into("delta", x, scratch, out, out_len, result, chunk_blocks)
 
     def compress_delta(self, x, chunk_blocks: int = 0):
-        """Compress a contiguous device tensor of 1-, 2-, 4- or 8-byte
-        elements into one delta frame: a uint8 device tensor of its exact
-        length.  One synchronisation, to read the length."""
-        t = self.torch
-        w = self._delta_elem_bytes(x)
-        scratch = t.empty(self.delta_scratch_bytes(x.numel(), w), dtype=t.uint8, device=self.device)
-        out = t.empty(self.delta_bound(x.numel(), w), dtype=t.uint8, device=self.device)
-        out_len = t.zeros(1, dtype=t.int64, device=self.device)
-        result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.compress_delta_into(x, scratch, out, out_len, result, chunk_blocks)
-        return out[: int(out_len.item())]
+        """`_elem_compress` into one delta frame."""
+        return self._elem_compress("delta", x, chunk_blocks)
 
     @staticmethod
     def delta_info(buf):
-        """`fsehip_delta_read_header` of a delta frame given as bytes, a numpy
-        array or a tensor (its first 48 bytes come to the host): (DeltaInfo,
-        the inner frame's FrameInfo); raises FseError (BAD_FRAME) otherwise."""
-        if hasattr(buf, "data_ptr"):  # a torch tensor
-            head = buf[:48].cpu().numpy().tobytes()
-        else:
-            head = bytes(memoryview(buf)[:48])
-        a = np.frombuffer(head, dtype=np.uint8)
-        info, inner = DeltaInfo(), FrameInfo()
-        check(load().fsehip_delta_read_header(_p(a), len(a), C.byref(info), C.byref(inner)),
-              "fsehip_delta_read_header")
-        return info, inner
+        """`fsehip_delta_read_header`: `_elem_info`, (DeltaInfo, FrameInfo)."""
+        return BlockCodec._elem_info("delta", buf)
 
     def decompress_delta_into(self, buf, info: DeltaInfo, inner: FrameInfo, scratch, out, block_status, result,
                               chunk_blocks: int = 0) -> None:
-        """`fsehip_delta_decompress`, no synchronisation: `scratch` >=
-        inner.n_total bytes, `out` info.n_elems elements (16-byte aligned),
-        `block_status` inner.n_blocks int32 or None, `result` two int32."""
-        check(self.lib.fsehip_delta_decompress(
-            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
-            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
-            out.numel() * out.element_size(),
-            C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
-            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_delta_decompress")
+        """`fsehip_delta_decompress`: `_elem_decompress_into` for a delta frame."""
+        self._elem_decompress_into("delta", buf, info, inner, scratch, out, block_status, result, chunk_blocks)
 
     def decompress_delta(self, buf, dtype, chunk_blocks: int = 0):
-        """Decode a delta frame (a uint8 device tensor) into a 1-D tensor of
-        `dtype`, whose size must be the frame's element width (ValueError
-        otherwise).  Returns (out, block_status); raises FseError for a
-        frame-level error (BAD_FRAME)."""
-        t = self.torch
-        info, inner = self.delta_info(buf)
-        self._check_dtype(info, dtype, "delta")
-        scratch = t.empty(inner.n_total, dtype=t.uint8, device=self.device)
-        out = t.empty(info.n_elems, dtype=dtype, device=self.device)
-        status = t.zeros(inner.n_blocks, dtype=t.int32, device=self.device)
-        result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_delta_into(buf, info, inner, scratch, out, status, result, chunk_blocks)
-        check(int(result[0].item()), "delta frame")
-        return out, status
+        """`_elem_decompress` of a delta frame: (out, block_status)."""
+        return self._elem_decompress("delta", buf, dtype, chunk_blocks)
 
     def delta_ranges_scratch_bytes(self, elem_bytes: int, ranges) -> int:
         """`fsehip_delta_ranges_scratch_bytes` for a sequence of triples or a `planes_ranges` array."""
-        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
-        n = 0 if getattr(arr, "empty", False) else len(arr)
-        return int(self.lib.fsehip_delta_ranges_scratch_bytes(elem_bytes, arr, n))
+        return self._elem_ranges_scratch_bytes("delta", elem_bytes, ranges)
 
     def decompress_delta_ranges_into(self, buf, info: DeltaInfo, inner: FrameInfo, ranges, scratch, out,
                                      range_status, result, chunk_blocks: int = 0) -> None:
-        """`fsehip_delta_decompress_ranges`, no synchronisation: `ranges` a
-        sequence of (elem_off, n_elems, dst_elem_off) or what `planes_ranges`
-        made of one; `scratch` >= delta_ranges_scratch_bytes; range r goes
-        to out[dst_elem_off: dst_elem_off + n_elems] (`out` of the frame's
-        element width, any alignment)."""
-        arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
-        n = 0 if getattr(arr, "empty", False) else len(arr)
-        check(self.lib.fsehip_delta_decompress_ranges(
-            C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(), arr, n,
-            C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
-            out.numel() * out.element_size(),
-            C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
-            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_delta_decompress_ranges")
+        """`fsehip_delta_decompress_ranges`: `_elem_decompress_ranges_into` for a delta frame."""
+        self._elem_decompress_ranges_into("delta", buf, info, inner, ranges, scratch, out, range_status, result,
+                                          chunk_blocks)
 
     def decompress_delta_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0):
-        """Decode the element ranges [(elem_off, count), ...] of a delta frame
-        without decoding the rest (each from its restart group's first
-        element on).  The ranges are packed back to back into one tensor of
-        `dtype`; returns (list of views of it, one per range, and the int32
-        range statuses).  Raises FseError for a frame-level error."""
-        t = self.torch
-        info, inner = self.delta_info(buf)
-        self._check_dtype(info, dtype, "delta")
-        packed, at = [], 0
-        for s, n in ranges:
-            packed.append((s, n, at))
-            at += n
-        arr = self.planes_ranges(packed)
-        scratch = t.empty(max(self.delta_ranges_scratch_bytes(info.elem_bytes, arr), 16), dtype=t.uint8,
-                          device=self.device)
-        out = t.empty(at, dtype=dtype, device=self.device)
-        status = t.zeros(len(packed), dtype=t.int32, device=self.device)
-        result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_delta_ranges_into(buf, info, inner, arr, scratch, out, status, result, chunk_blocks)
-        check(int(result[0].item()), "delta frame")
-        return [out[d: d + n] for _, n, d in packed], status
+        """`_elem_decompress_ranges` of a delta frame: (views, range statuses)."""
+        return self._elem_decompress_ranges("delta", buf, dtype, ranges, chunk_blocks)
 
     def decompress_delta_range(self, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0):
-        """Elements [elem_off, elem_off + count) of a delta frame as a tensor
-        of `dtype`; raises FseError for a frame-level error or with the
-        status of the first failed block the range needs."""
-        views, status = self.decompress_delta_ranges(buf, dtype, [(elem_off, count)], chunk_blocks)
-        check(int(status[0].item()), "delta frame range")
-        return views[0]
+        """`_elem_decompress_range` of a delta frame: one tensor."""
+        return self._elem_decompress_range("delta", buf, dtype, elem_off, count, chunk_blocks)
 
     # ------------------------------------------------------------ the check record and sealed buffers
     # fsehip.h section 2f: a CRC-32 (zlib's) per check block of the content,
@@ -1199,17 +1176,14 @@ class BlockCodec:
             if x.element_size() != 1:
                 raise ValueError("a sealed frame takes a 1-byte tensor; wider elements go to kind='planes' or 'delta'")
             return 1
-        if kind == "planes":
-            return self._elem_bytes(x)
-        if kind == "delta":
-            return self._delta_elem_bytes(x)
-        raise ValueError(f"kind {kind!r}: 'frame', 'planes' or 'delta'")
+        if kind not in _ELEM:
+            raise ValueError(f"kind {kind!r}: 'frame', 'planes' or 'delta'")
+        return self._elem_width(kind, x)
 
     def sealed_bound(self, x, kind: str = "frame", check_block: int = 65536) -> int:
         """A capacity no sealed buffer of `x` exceeds: the record, then the container's bound."""
         w = self._sealed_kind(x, kind)
-        inner = {"frame": lambda: self.frame_bound(x.numel()), "planes": lambda: self.planes_bound(x.numel(), w),
-                 "delta": lambda: self.delta_bound(x.numel(), w)}[kind]()
+        inner = self.frame_bound(x.numel()) if kind == "frame" else self._elem_bound(kind, x.numel(), w)
         return self.check_bytes(self._content_bytes(x), check_block) + inner
 
     def compress_sealed_into(self, x, kind, buf, out_len, result, scratch=None, check_block: int = 65536,
@@ -1225,10 +1199,8 @@ class BlockCodec:
         self.check_build_into(x, buf[:rec], check_block)
         if kind == "frame":
             self.compress_frame_into(x, buf[rec:], out_len, result, chunk_blocks)
-        elif kind == "planes":
-            self.compress_planes_into(x, scratch, buf[rec:], out_len, result, chunk_blocks)
         else:
-            self.compress_delta_into(x, scratch, buf[rec:], out_len, result, chunk_blocks)
+            self._elem_compress_into(kind, x, scratch, buf[rec:], out_len, result, chunk_blocks)
         return rec
 
     def compress_sealed(self, x, kind: str = "frame", check_block: int = 65536, chunk_blocks: int = 0):
@@ -1239,8 +1211,7 @@ class BlockCodec:
         w = self._sealed_kind(x, kind)
         scratch = None
         if kind != "frame":
-            need = (self.planes_scratch_bytes if kind == "planes" else self.delta_scratch_bytes)(x.numel(), w)
-            scratch = t.empty(need, dtype=t.uint8, device=self.device)
+            scratch = t.empty(self._elem_scratch_bytes(kind, x.numel(), w), dtype=t.uint8, device=self.device)
         buf = t.empty(self.sealed_bound(x, kind, check_block), dtype=t.uint8, device=self.device)
         out_len = t.zeros(1, dtype=t.int64, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
@@ -1274,14 +1245,13 @@ class BlockCodec:
             if dtype is not None and t.empty(0, dtype=dtype).element_size() != 1:
                 raise ValueError(f"dtype {dtype}: a sealed frame holds bytes")
             return dtype or t.uint8
-        w = (self.planes_info if kind == "planes" else self.delta_info)(inner)[0].elem_bytes
-        return dtype or {1: t.uint8, 2: t.int16, 4: t.int32, 8: t.int64}[w]
+        return dtype or {1: t.uint8, 2: t.int16, 4: t.int32, 8: t.int64}[self._elem_info(kind, inner)[0].elem_bytes]
 
     def sealed_inner_info(self, kind: str, inner):
         """The container's own header(s) at the start of `inner` (bytes, numpy
         or a tensor): FrameInfo for a frame, (PlanesInfo | DeltaInfo,
         FrameInfo) otherwise."""
-        return {"frame": self.frame_info, "planes": self.planes_info, "delta": self.delta_info}[kind](inner)
+        return self.frame_info(inner) if kind == "frame" else self._elem_info(kind, inner)
 
     def decompress_sealed_into(self, buf, sealed, inner_info, out, block_status, result, check_status, check_result,
                                scratch=None, chunk_blocks: int = 0) -> None:
@@ -1295,10 +1265,8 @@ class BlockCodec:
         inner = buf[off:]
         if kind == "frame":
             self.decompress_frame_into(inner, inner_info, out, block_status, result, chunk_blocks)
-        elif kind == "planes":
-            self.decompress_planes_into(inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
         else:
-            self.decompress_delta_into(inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
+            self._elem_decompress_into(kind, inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
         self.check_verify_into(buf, info, out, check_status, check_result)
 
     def decompress_sealed(self, buf, dtype=None, chunk_blocks: int = 0, with_result: bool = False):
@@ -1317,7 +1285,7 @@ class BlockCodec:
             finfo = inner_info
             out = t.empty(info.n_content, dtype=dt, device=self.device)
         else:
-            self._check_dtype(inner_info[0], dt, "plane" if kind == "planes" else "delta")
+            self._check_dtype(inner_info[0], dt, _ELEM[kind].label)
             finfo = inner_info[1]
             scratch = t.empty(finfo.n_total, dtype=t.uint8, device=self.device)
             out = t.empty(inner_info[0].n_elems, dtype=dt, device=self.device)
@@ -1357,13 +1325,12 @@ class BlockCodec:
         if kind == "frame":
             self.decompress_frame_ranges_into(inner, self.frame_info(inner), packed, out, status, result, chunk_blocks)
         else:
-            pinfo, finfo = (self.planes_info if kind == "planes" else self.delta_info)(inner)
-            self._check_dtype(pinfo, dt, "plane" if kind == "planes" else "delta")
+            pinfo, finfo = self._elem_info(kind, inner)
+            self._check_dtype(pinfo, dt, _ELEM[kind].label)
             arr = self.planes_ranges(packed)
-            need = (self.planes_ranges_scratch_bytes if kind == "planes" else self.delta_ranges_scratch_bytes)(w, arr)
-            scratch = t.empty(max(need, 16), dtype=t.uint8, device=self.device)
-            call = self.decompress_planes_ranges_into if kind == "planes" else self.decompress_delta_ranges_into
-            call(inner, pinfo, finfo, arr, scratch, out, status, result, chunk_blocks)
+            scratch = t.empty(max(self._elem_ranges_scratch_bytes(kind, w, arr), 16), dtype=t.uint8, device=self.device)
+            self._elem_decompress_ranges_into(kind, inner, pinfo, finfo, arr, scratch, out, status, result,
+                                              chunk_blocks)
         check(int(result[0].item()), f"sealed {kind}")
         check_status = t.zeros(len(packed), dtype=t.int32, device=self.device)
         check_result = t.zeros(2, dtype=t.int32, device=self.device)
@@ -1495,9 +1462,7 @@ class BlockCodec:
             t = self.torch  # (an empty tensor has no stride to view through)
             raw = x.reshape(-1).view(t.uint8) if x.numel() else t.empty(0, dtype=t.uint8, device=self.device)
             return self.compress_frame(raw, chunk_blocks), kind
-        if kind == "planes":
-            return self.compress_planes(x, chunk_blocks), kind
-        return self.compress_delta(x, chunk_blocks), kind
+        return self._elem_compress(kind, x, chunk_blocks), kind
 
     def decompress_auto(self, buf, dtype, chunk_blocks: int = 0):
         """Decode a frame, plane frame or delta frame (a uint8 device tensor)
@@ -1506,10 +1471,8 @@ class BlockCodec:
         bytes are viewed as `dtype` (ValueError when they are no whole number
         of elements)."""
         kind = container_kind(buf)
-        if kind == "planes":
-            return self.decompress_planes(buf, dtype, chunk_blocks)
-        if kind == "delta":
-            return self.decompress_delta(buf, dtype, chunk_blocks)
+        if kind in _ELEM:
+            return self._elem_decompress(kind, buf, dtype, chunk_blocks)
         if kind != "frame":
             raise ValueError("a sealed buffer goes to decompress_sealed")
         out, status = self.decompress_frame(buf, chunk_blocks)
@@ -1568,82 +1531,65 @@ def frame_decompress_range(data, offset: int, length: int, device=None) -> bytes
     return codec.decompress_frame_range(frame, offset, length).cpu().numpy().tobytes()
 
 
-def planes_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
-                    device=None) -> bytes:
-    """Compress a numpy array of item size 2, 4 or 8 into one plane frame
-    (fsehip.h section 2d) on the GPU; copies through torch.  The element width
-    is stored, the dtype and the shape are not."""
-    import torch
-
-    a = np.ascontiguousarray(data)
-    if a.dtype.itemsize not in (2, 4, 8):
-        raise ValueError(f"item size {a.dtype.itemsize}: the plane frame takes 2, 4 or 8 bytes")
-    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
-                       nstates=nstates)
-    view = {2: np.int16, 4: np.int32, 8: np.int64}[a.dtype.itemsize]
-    src = torch.from_numpy(a.reshape(-1).view(view).copy()).to(codec.device)
-    return codec.compress_planes(src).cpu().numpy().tobytes()
-
-
-def planes_decompress(data, dtype, device=None) -> np.ndarray:
-    """Decode a plane frame held in host memory into a 1-D numpy array of
-    `dtype` (its item size must be the frame's element width); raises FseError
-    on a frame-level error or with the first failed block's status."""
-    import torch
-
-    dt = np.dtype(dtype)
-    codec = BlockCodec(device=device)
-    info, _ = BlockCodec.planes_info(_buf(data))  # not a plane frame: BAD_FRAME before any device work
-    if dt.itemsize != info.elem_bytes:
-        raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the plane frame holds {info.elem_bytes}-byte ones")
-    buf = torch.from_numpy(_buf(data).copy()).to(codec.device)
-    view = {2: torch.int16, 4: torch.int32, 8: torch.int64}[info.elem_bytes]
-    out, status = codec.decompress_planes(buf, view)
-    st = status.cpu().numpy()
-    if st.any():
-        b = int(np.flatnonzero(st)[0])
-        raise FseError(int(st[b]), f"plane frame block {b}")
-    return out.cpu().numpy().view(dt)
-
-
 # the integer view a host array of each item size travels as
 _INT_VIEW = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}
 
 
-def delta_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
-                   device=None) -> bytes:
-    """Compress a numpy array of item size 1, 2, 4 or 8 into one delta frame
-    (fsehip.h section 2e) on the GPU; copies through torch.  The element width
-    is stored, the dtype and the shape are not."""
+def _elem_compress(kind: str, data, block_size: int, table_log: int, ckpt_interval: int, nstates: int, device) -> bytes:
+    """Compress a numpy array of one of the kind's item sizes into one frame
+    of the kind on the GPU; copies through torch.  The element width is
+    stored, the dtype and the shape are not."""
     import torch
 
     a = np.ascontiguousarray(data)
-    if a.dtype.itemsize not in _INT_VIEW:
-        raise ValueError(f"item size {a.dtype.itemsize}: the delta frame takes 1, 2, 4 or 8 bytes")
+    if a.dtype.itemsize not in _ELEM[kind].widths:
+        raise ValueError(f"item size {a.dtype.itemsize}: the {_ELEM[kind].label} frame takes {_ELEM[kind].takes} bytes")
     codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
                        nstates=nstates)
     src = torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device)
-    return codec.compress_delta(src).cpu().numpy().tobytes()
+    return codec._elem_compress(kind, src).cpu().numpy().tobytes()
 
 
-def delta_decompress(data, dtype, device=None) -> np.ndarray:
-    """Decode a delta frame held in host memory into a 1-D numpy array of
-    `dtype` (its item size must be the frame's element width); raises FseError
-    on a frame-level error or with the first failed block's status."""
+def _elem_decompress(kind: str, data, dtype, device) -> np.ndarray:
+    """Decode a frame of the kind held in host memory into a 1-D numpy array
+    of `dtype` (its item size must be the frame's element width); raises
+    FseError on a frame-level error or with the first failed block's status."""
     import torch
 
-    dt = np.dtype(dtype)
+    dt, label = np.dtype(dtype), _ELEM[kind].label
     codec = BlockCodec(device=device)
-    info, _ = BlockCodec.delta_info(_buf(data))  # not a delta frame: BAD_FRAME before any device work
+    info, _ = BlockCodec._elem_info(kind, _buf(data))  # not a frame of the kind: BAD_FRAME before any device work
     if dt.itemsize != info.elem_bytes:
-        raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the delta frame holds {info.elem_bytes}-byte ones")
+        raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the {label} frame holds {info.elem_bytes}-byte ones")
     buf = torch.from_numpy(_buf(data).copy()).to(codec.device)
-    out, status = codec.decompress_delta(buf, getattr(torch, np.dtype(_INT_VIEW[info.elem_bytes]).name))
+    out, status = codec._elem_decompress(kind, buf, getattr(torch, np.dtype(_INT_VIEW[info.elem_bytes]).name))
     st = status.cpu().numpy()
     if st.any():
         b = int(np.flatnonzero(st)[0])
-        raise FseError(int(st[b]), f"delta frame block {b}")
+        raise FseError(int(st[b]), f"{label} frame block {b}")
     return out.cpu().numpy().view(dt)
+
+
+def planes_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
+                    device=None) -> bytes:
+    """`_elem_compress` of a numpy array of item size 2, 4 or 8 into one plane frame (fsehip.h section 2d)."""
+    return _elem_compress("planes", data, block_size, table_log, ckpt_interval, nstates, device)
+
+
+def planes_decompress(data, dtype, device=None) -> np.ndarray:
+    """`_elem_decompress` of a plane frame held in host memory."""
+    return _elem_decompress("planes", data, dtype, device)
+
+
+def delta_compress(data, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
+                   device=None) -> bytes:
+    """`_elem_compress` of a numpy array of item size 1, 2, 4 or 8 into one delta frame (fsehip.h section 2e)."""
+    return _elem_compress("delta", data, block_size, table_log, ckpt_interval, nstates, device)
+
+
+def delta_decompress(data, dtype, device=None) -> np.ndarray:
+    """`_elem_decompress` of a delta frame held in host memory."""
+    return _elem_decompress("delta", data, dtype, device)
 
 
 # ---------------------------------------------------------------- the size estimate and the automatic choice
@@ -1707,10 +1653,8 @@ def auto_decompress(blob, dtype, device=None) -> np.ndarray:
     array of `dtype`; raises FseError as frame_decompress / planes_decompress
     / delta_decompress."""
     kind = container_kind(_buf(blob))
-    if kind == "planes":
-        return planes_decompress(blob, dtype, device)
-    if kind == "delta":
-        return delta_decompress(blob, dtype, device)
+    if kind in _ELEM:
+        return _elem_decompress(kind, blob, dtype, device)
     if kind != "frame":
         raise ValueError("a sealed buffer goes to sealed_decompress")
     return np.frombuffer(frame_decompress(blob, device), dtype=np.dtype(dtype))

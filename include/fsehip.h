@@ -966,11 +966,7 @@ int fsehip_planes_decompress_ranges(const fsehip_planes_info* info, const fsehip
 
 #define FSEHIP_DELTA_RESTART 4096u /* elements between restarts, version 1 */
 
-typedef struct {
-    uint32_t version, elem_bytes, reserved, pad_; /* pad_ is not stored */
-    uint64_t n_elems;
-    uint64_t stride; /* roundup(n_elems, 16): derived, not stored */
-} fsehip_delta_info;
+typedef fsehip_planes_info fsehip_delta_info; /* the same fields (section 2d) */
 
 /* 16 + fsehip_frame_bound(w * stride, block_size): a capacity no delta frame
  * of n_elems elements exceeds.  0 for elem_bytes outside {1, 2, 4, 8} or when

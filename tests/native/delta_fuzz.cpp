@@ -1,4 +1,4 @@
-// Fuzz of the delta frame's host code (entropy_coders_amd/csrc/fse_delta.cpp
+// Fuzz of the delta frame's host code (entropy_coders_amd/csrc/fse_elem.cpp
 // over fse_frame.cpp, include/fsehip.h section 2e), built by
 // tests/test_delta_sanitized.py with AddressSanitizer + UBSan: valid, random,
 // truncated and bit-flipped 48-byte heads are parsed from heap buffers
@@ -13,7 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 
-#include "../../entropy_coders_amd/csrc/fse_delta_host.h"
+#include "../../entropy_coders_amd/csrc/fse_elem_host.h"
 #include "../../include/fsehip.h"
 
 static uint64_t rng_state = 0x9E3779B97F4A7C15ull;

@@ -1,4 +1,4 @@
-// Fuzz of the plane frame's host code (entropy_coders_amd/csrc/fse_planes.cpp
+// Fuzz of the plane frame's host code (entropy_coders_amd/csrc/fse_elem.cpp
 // over fse_frame.cpp, include/fsehip.h section 2d), built by
 // tests/test_planes_sanitized.py with AddressSanitizer + UBSan: valid, random,
 // truncated and bit-flipped 48-byte heads are parsed from heap buffers

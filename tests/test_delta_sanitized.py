@@ -3,7 +3,7 @@ tests/native/delta_fuzz.cpp, a stand-alone program, feeds
 fsehip_delta_read_header valid, random, truncated and bit-flipped 48-byte
 heads from exact-size heap buffers, and random range lists to the
 range-scratch formula and the range checks
-(entropy_coders_amd/csrc/fse_delta.cpp and fse_frame.cpp have no HIP include
+(entropy_coders_amd/csrc/fse_elem.cpp and fse_frame.cpp have no HIP include
 and build with g++ alone): every header result is FSE_OK with its fields in
 range, or BAD_FRAME; every range result equals a 128-bit restatement."""
 import os
@@ -22,7 +22,7 @@ def test_delta_header_and_ranges_sanitized(tmp_path):
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined",
                     "-fno-sanitize-recover=all", "-o", str(exe),
                     os.path.join(ROOT, "tests", "native", "delta_fuzz.cpp"),
-                    os.path.join(csrc, "fse_delta.cpp"), os.path.join(csrc, "fse_frame.cpp")],
+                    os.path.join(csrc, "fse_elem.cpp"), os.path.join(csrc, "fse_frame.cpp")],
                    check=True, capture_output=True, timeout=300)
     env = dict(os.environ, ASAN_OPTIONS="verify_asan_link_order=0")
     r = subprocess.run([str(exe), "20000"], capture_output=True, text=True, timeout=300, env=env)
