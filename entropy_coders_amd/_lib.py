@@ -54,6 +54,9 @@ EXPORTS = (
     "fsehip_delta_bound", "fsehip_delta_scratch_bytes", "fsehip_delta_read_header", "fsehip_delta_write_header",
     "fsehip_delta_encode", "fsehip_delta_decode", "fsehip_delta_compress", "fsehip_delta_decompress",
     "fsehip_delta_ranges_scratch_bytes", "fsehip_delta_decompress_ranges",
+    "fsehip_diff_bound", "fsehip_diff_scratch_bytes", "fsehip_diff_read_header", "fsehip_diff_write_header",
+    "fsehip_diff_encode", "fsehip_diff_decode", "fsehip_diff_compress", "fsehip_diff_decompress",
+    "fsehip_diff_ranges_scratch_bytes", "fsehip_diff_decompress_ranges",
     "fsehip_crc32", "fsehip_crc32_combine", "fsehip_check_bytes", "fsehip_check_read_header",
     "fsehip_check_write_header", "fsehip_sealed_read_header", "fsehip_check_build", "fsehip_check_verify",
     "fsehip_check_ranges_verified_bytes", "fsehip_check_verify_ranges",
@@ -111,7 +114,7 @@ class FrameParams(C.Structure):
 
 
 class PlanesInfo(C.Structure):
-    """fsehip_planes_info: a plane or delta frame's header fields, stride = roundup(n_elems, 16)."""
+    """fsehip_planes_info: a plane, delta or diff frame's header fields, stride = roundup(n_elems, 16)."""
     _fields_ = [("version", C.c_uint32), ("elem_bytes", C.c_uint32), ("reserved", C.c_uint32), ("pad_", C.c_uint32),
                 ("n_elems", C.c_uint64), ("stride", C.c_uint64)]
 
@@ -125,10 +128,11 @@ DELTA_RESTART = 4096  # FSEHIP_DELTA_RESTART: elements between the delta frame's
 
 
 DeltaInfo = PlanesInfo  # fsehip_delta_info is a typedef of fsehip_planes_info
+DiffInfo = PlanesInfo   # and so is fsehip_diff_info
 
 
 CHECK_CRC32 = 1  # FSEHIP_CHECK_CRC32: the check record's algorithm
-SEALED_KINDS = ("frame", "planes", "delta")  # FSEHIP_SEALED_FRAME / _PLANES / _DELTA
+SEALED_KINDS = ("frame", "planes", "delta", "diff")  # FSEHIP_SEALED_FRAME / _PLANES / _DELTA / _DIFF
 
 
 class CheckInfo(C.Structure):
@@ -140,6 +144,7 @@ class CheckInfo(C.Structure):
 
 KINDS = ("frame", "planes", "delta")  # FSEHIP_KIND_FRAME / _PLANES / _DELTA
 KIND_SEALED = 3                        # FSEHIP_KIND_SEALED: fsehip_container_kind of an "FSEK" buffer
+KIND_DIFF = 4                          # FSEHIP_KIND_DIFF: of an "FSEB" buffer; no estimate takes it
 EST_NONE = (1 << 64) - 1               # FSEHIP_EST_NONE
 EST_RAW, EST_RLE, EST_FSE = 0, 1, 2    # FSEHIP_EST_*: the frame directory's block types
 
@@ -277,6 +282,20 @@ def load() -> C.CDLL:
         fn("ranges_scratch_bytes").argtypes = [u32, PR, u32]
         fn("ranges_scratch_bytes").restype = u64
         fn("decompress_ranges").argtypes = [PI, FI, u32, P, u64, PR, u32, P, u64, P, u64, P, P, P]
+    # the diff frame: the same ten, with the base after the source or destination pointer
+    lib.fsehip_diff_bound.argtypes = [u64, u32, u32]
+    lib.fsehip_diff_bound.restype = u64
+    lib.fsehip_diff_scratch_bytes.argtypes = [u64, u32]
+    lib.fsehip_diff_scratch_bytes.restype = u64
+    lib.fsehip_diff_read_header.argtypes = [P, sz, PI, FI]
+    lib.fsehip_diff_write_header.argtypes = [PI, P]
+    lib.fsehip_diff_encode.argtypes = [u32, P, P, u64, P, P]
+    lib.fsehip_diff_decode.argtypes = [u32, P, u64, P, P, P]
+    lib.fsehip_diff_compress.argtypes = [C.POINTER(FrameParams), u32, P, P, u64, P, u64, P, u64, P, P, P]
+    lib.fsehip_diff_decompress.argtypes = [PI, FI, u32, P, u64, P, u64, P, P, u64, P, P, P]
+    lib.fsehip_diff_ranges_scratch_bytes.argtypes = [u32, PR, u32]
+    lib.fsehip_diff_ranges_scratch_bytes.restype = u64
+    lib.fsehip_diff_decompress_ranges.argtypes = [PI, FI, u32, P, u64, PR, u32, P, u64, P, P, u64, P, P, P]
     CI = C.POINTER(CheckInfo)
     lib.fsehip_crc32.argtypes = [u32, P, sz]
     lib.fsehip_crc32.restype = u32

@@ -129,9 +129,9 @@ int fsehip_sealed_read_header(const uint8_t* buf, size_t len, fsehip_check_info*
         if (left < 32u) return FSE_ERR_BAD_FRAME;
         k = FSEHIP_SEALED_FRAME;
         for (int i = 7; i >= 0; --i) content = (content << 8) | in[16 + i];  // n_total
-    } else if (in[3] == 'P' || in[3] == 'D') {
+    } else if (in[3] == 'P' || in[3] == 'D' || in[3] == 'B') {
         if (left < 48u) return FSE_ERR_BAD_FRAME;
-        k = in[3] == 'P' ? FSEHIP_SEALED_PLANES : FSEHIP_SEALED_DELTA;
+        k = in[3] == 'P' ? FSEHIP_SEALED_PLANES : in[3] == 'D' ? FSEHIP_SEALED_DELTA : FSEHIP_SEALED_DIFF;
         const uint64_t w = in[5];
         uint64_t n_elems = 0;
         for (int i = 7; i >= 0; --i) n_elems = (n_elems << 8) | in[8 + i];

@@ -1,12 +1,13 @@
 // fse_elem.cpp -- the header, sizes and range checks of the element frames,
-// host side: the plane frame (fsehip.h section 2d) and the delta frame
-// (section 2e) are the same 16 header bytes over one frame of section 2b and
-// differ in what an ElemKind says.
+// host side: the plane frame (fsehip.h section 2d), the delta frame (section
+// 2e) and the diff frame (section 2h) are the same 16 header bytes over one
+// frame of section 2b and differ in what an ElemKind says.
 //
 // Plain C++ with no HIP include, as fse_frame.cpp: the same source builds
 // into libfsehip.so and, with g++ alone, into the sanitizer fuzzes of
-// tests/native/planes_fuzz.cpp and delta_fuzz.cpp.  The kernels are
-// fse_planes.hip and fse_delta.hip, the device calls fse_capi_elem.cpp.
+// tests/native/planes_fuzz.cpp, delta_fuzz.cpp and diff_fuzz.cpp.  The kernels
+// are fse_planes.hip, fse_delta.hip and fse_diff.hip, the device calls
+// fse_capi_elem.cpp.
 #include <string.h>
 
 #include <algorithm>
@@ -94,7 +95,7 @@ int elem_write_header(const ElemKind& K, const fsehip_planes_info* info, uint8_t
 
 // Per range w plane pieces, 16-byte aligned for the merge's loads, then the
 // w * n_ranges statuses of the frame call.  A plane range's pieces hold
-// n_elems bytes each, back to back.  A delta range is decoded from its restart
+// n_elems bytes each, back to back, and so do a diff range's.  A delta range is decoded from its restart
 // group's first element e0, so its pieces hold (elem_off - e0) + n_elems bytes
 // each, every one 16-byte aligned.
 uint64_t elem_ranges_scratch_bytes(const ElemKind& K, uint32_t elem_bytes, const fsehip_planes_range* ranges,
@@ -181,6 +182,18 @@ uint64_t fsehip_planes_ranges_scratch_bytes(uint32_t w, const fsehip_planes_rang
 }
 uint64_t fsehip_delta_ranges_scratch_bytes(uint32_t w, const fsehip_planes_range* ranges, uint32_t n_ranges) {
     return elem_ranges_scratch_bytes(kDelta, w, ranges, n_ranges);
+}
+
+uint64_t fsehip_diff_scratch_bytes(uint64_t n, uint32_t w) { return elem_scratch_bytes(kDiff, n, w); }
+uint64_t fsehip_diff_bound(uint64_t n, uint32_t w, uint32_t bs) { return elem_bound(kDiff, n, w, bs); }
+int fsehip_diff_read_header(const uint8_t* hdr, size_t len, fsehip_diff_info* out, fsehip_frame_info* inner) {
+    return elem_read_header(kDiff, hdr, len, out, inner);
+}
+int fsehip_diff_write_header(const fsehip_diff_info* info, uint8_t hdr[16]) {
+    return elem_write_header(kDiff, info, hdr);
+}
+uint64_t fsehip_diff_ranges_scratch_bytes(uint32_t w, const fsehip_planes_range* ranges, uint32_t n_ranges) {
+    return elem_ranges_scratch_bytes(kDiff, w, ranges, n_ranges);
 }
 
 }  // extern "C"

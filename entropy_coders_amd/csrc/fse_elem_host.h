@@ -1,8 +1,9 @@
 // fse_elem_host.h -- what the element frames' translation units share: the
-// plane frame (fsehip.h section 2d) and the delta frame (section 2e) are one
-// container, 16 header bytes and one frame of section 2b over a byte-plane
-// image, told apart by an ElemKind.  The host checks of fse_elem.cpp and the
-// launchers of fse_planes.hip and fse_delta.hip, called by fse_capi_elem.cpp.
+// plane frame (fsehip.h section 2d), the delta frame (section 2e) and the diff
+// frame (section 2h) are one container, 16 header bytes and one frame of
+// section 2b over a byte-plane image, told apart by an ElemKind.  The host
+// checks of fse_elem.cpp and the launchers of fse_planes.hip, fse_delta.hip
+// and fse_diff.hip, called by fse_capi_elem.cpp.
 // Plain C++ with no HIP include (a stream travels as void*), so that
 // fse_elem.cpp builds with g++ alone.  Not part of the public ABI.
 #pragma once
@@ -19,10 +20,11 @@ struct ElemKind {
 };
 constexpr ElemKind kPlanes{'P', 1u << 2 | 1u << 4 | 1u << 8, false};
 constexpr ElemKind kDelta{'D', 1u << 1 | 1u << 2 | 1u << 4 | 1u << 8, true};
+constexpr ElemKind kDiff{'B', 1u << 1 | 1u << 2 | 1u << 4 | 1u << 8, false};  // 'B': against a base
 
 inline bool width_ok(const ElemKind& K, uint32_t w) { return w <= 8u && (K.widths >> w & 1u); }
 
-// The exported host calls of sections 2d and 2e, by kind.
+// The exported host calls of sections 2d, 2e and 2h, by kind.
 uint64_t elem_scratch_bytes(const ElemKind& K, uint64_t n_elems, uint32_t elem_bytes);
 uint64_t elem_bound(const ElemKind& K, uint64_t n_elems, uint32_t elem_bytes, uint32_t block_size);
 int elem_read_header(const ElemKind& K, const uint8_t* hdr, size_t len, fsehip_planes_info* out,
@@ -75,6 +77,15 @@ struct DeltaPieces {
     uint32_t n;
 };
 
+// The diff frame's: PlanePieces, and range i's first element in the base.
+struct DiffPieces {
+    uint64_t off[kPlanePieces];
+    uint64_t count[kPlanePieces];
+    uint64_t dst[kPlanePieces];
+    uint64_t src[kPlanePieces];
+    uint32_t n;
+};
+
 // The launchers return an FSE status (FSE_OK or FSE_ERR_HIP).  `stream` is a
 // hipStream_t.  w is one of the kind's widths.
 int launch_planes_split(uint32_t w, const void* src, uint64_t n_elems, uint8_t* image, void* stream);
@@ -88,7 +99,15 @@ int launch_planes_pieces(uint32_t w, const uint8_t* scratch, const PlanePieces& 
                          const int32_t* result, void* stream);
 int launch_delta_pieces(uint32_t w, const uint8_t* scratch, const DeltaPieces& P, uint8_t* dst,
                         const int32_t* result, void* stream);
-// The three below serve both kinds (fse_planes.hip).
+// The diff frame's take the base tensor, n_elems elements aligned to w; the
+// merge's dst may be the base itself (fse_diff.hip).  Range i of the pieces
+// reads the base from element P.src[i] on.
+int launch_diff_split(uint32_t w, const void* src, const void* base, uint64_t n_elems, uint8_t* image, void* stream);
+int launch_diff_merge(uint32_t w, const uint8_t* image, const void* base, uint64_t n_elems, void* dst,
+                      const int32_t* result, void* stream);
+int launch_diff_pieces(uint32_t w, const uint8_t* scratch, const DiffPieces& P, const void* base, uint8_t* dst,
+                       const int32_t* result, void* stream);
+// The three below serve every kind (fse_planes.hip).
 // encode: *out_len += 16 and the 16 header bytes at `out`
 int launch_elem_finish(const uint8_t hdr[16], uint8_t* out, uint64_t* out_len, void* stream);
 // decode, after the frame call: the 16 bytes at `in` against `hdr`; on a

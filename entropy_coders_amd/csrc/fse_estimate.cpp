@@ -84,6 +84,7 @@ int fsehip_container_kind(const uint8_t* buf, size_t len) {
         case 'P': return (int)FSEHIP_KIND_PLANES;
         case 'D': return (int)FSEHIP_KIND_DELTA;
         case 'K': return (int)FSEHIP_KIND_SEALED;
+        case 'B': return (int)FSEHIP_KIND_DIFF;
         default: return FSE_ERR_BAD_FRAME;
     }
 }

@@ -11,9 +11,10 @@ import threading
 
 import numpy as np
 
-from ._lib import (EST_NONE, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState, BitStackWriterState,
-                   BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, EncodeTable, FrameInfo, FrameParams,
-                   FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check, load)
+from ._lib import (EST_NONE, KIND_DIFF, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState, BitStackWriterState,
+                   BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, DiffInfo, EncodeTable, FrameInfo,
+                   FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check,
+                   load)
 
 
 def _buf(data) -> np.ndarray:
@@ -27,18 +28,21 @@ def _p(a: np.ndarray):
 
 
 class _ElemKind:
-    """What tells the two element frames (fsehip.h sections 2d, 2e) apart:
+    """What tells the element frames (fsehip.h sections 2d, 2e, 2h) apart:
     the C names' prefix and their names of the two bare transforms, the
-    element widths taken, the info class and the label used in messages."""
+    element widths taken, the info class, the label used in messages and
+    whether the calls take a base tensor (after the source or destination
+    pointer)."""
 
-    def __init__(self, prefix: str, split: str, merge: str, widths: tuple, info, label: str):
+    def __init__(self, prefix: str, split: str, merge: str, widths: tuple, info, label: str, based: bool = False):
         self.prefix, self.split, self.merge = prefix, split, merge
-        self.widths, self.info, self.label = widths, info, label
+        self.widths, self.info, self.label, self.based = widths, info, label, based
         self.takes = ", ".join(map(str, widths[:-1])) + f" or {widths[-1]}"  # "2, 4 or 8"
 
 
 _ELEM = {"planes": _ElemKind("fsehip_planes_", "split", "merge", (2, 4, 8), PlanesInfo, "plane"),
-         "delta": _ElemKind("fsehip_delta_", "encode", "decode", (1, 2, 4, 8), DeltaInfo, "delta")}
+         "delta": _ElemKind("fsehip_delta_", "encode", "decode", (1, 2, 4, 8), DeltaInfo, "delta"),
+         "diff": _ElemKind("fsehip_diff_", "encode", "decode", (1, 2, 4, 8), DiffInfo, "diff", based=True)}
 
 _tls = threading.local()
 
@@ -795,8 +799,13 @@ class BlockCodec:
     # neighbouring elements, with a restart every 4,096: for integer tensors
     # that grow (sorted ids, offsets, timestamps); any dtype of 1, 2, 4 or 8
     # bytes round-trips, floats gain nothing.  The container stores the element
-    # width; dtype and shape stay with the caller.  The `_elem_*` methods take
-    # the kind, "planes" or "delta" (a row of _ELEM); the public names forward.
+    # width; dtype and shape stay with the caller.  The diff frame (section 2h)
+    # takes the zigzag differences against a base tensor of the same dtype and
+    # element count that the receiver already holds, and needs that base to
+    # decode; the container does not identify it (a sealed buffer's checksums
+    # tell a wrong one).  The `_elem_*` methods take the kind, "planes",
+    # "delta" or "diff" (a row of _ELEM), and `base` for "diff" alone; the
+    # public names forward.
     def _elem_fn(self, kind: str, name: str):
         return getattr(self.lib, _ELEM[kind].prefix + name)
 
@@ -814,49 +823,80 @@ class BlockCodec:
             raise ValueError(f"compress_{kind} needs a contiguous tensor")
         return w
 
+    def _elem_base(self, kind: str, base, n_elems: int, dtype) -> tuple:
+        """The base argument of a call of the kind: () for a kind without one,
+        else the base's pointer after these checks (ValueError): a contiguous
+        device tensor of `dtype` and n_elems elements."""
+        if not _ELEM[kind].based:
+            if base is not None:
+                raise ValueError(f"the {_ELEM[kind].label} frame takes no base")
+            return ()
+        if base is None:
+            raise ValueError("the diff frame needs its base tensor")
+        if not hasattr(base, "data_ptr") or not base.is_cuda:
+            raise ValueError("base must be a device tensor")
+        if not base.is_contiguous():
+            raise ValueError("base must be contiguous")
+        if base.dtype != dtype or base.numel() != n_elems:
+            raise ValueError(f"base has {base.numel()} elements of {base.dtype}, the tensor {n_elems} of {dtype}")
+        return (C.c_void_p(base.data_ptr()),)
+
+    def _elem_out(self, out, n_elems: int, dtype):
+        """The caller's `out` of a decode after its checks, or a fresh tensor."""
+        if out is None:
+            return self.torch.empty(n_elems, dtype=dtype, device=self.device)
+        if not out.is_contiguous() or out.dtype != dtype or out.numel() != n_elems:
+            raise ValueError(f"out must be a contiguous tensor of {n_elems} elements of {dtype}")
+        return out
+
     def _elem_bound(self, kind: str, n_elems: int, elem_bytes: int) -> int:
         return int(self._elem_fn(kind, "bound")(n_elems, elem_bytes, self.block_size))
 
     def _elem_scratch_bytes(self, kind: str, n_elems: int, elem_bytes: int) -> int:
         return int(self._elem_fn(kind, "scratch_bytes")(n_elems, elem_bytes))
 
-    def _elem_split(self, kind: str, x):
+    def _elem_split(self, kind: str, x, base=None):
         """The image of a contiguous device tensor (uint8, pads zeroed)."""
         w = self._elem_width(kind, x)
+        b = self._elem_base(kind, base, x.numel(), x.dtype)
         image = self.torch.empty(self._elem_scratch_bytes(kind, x.numel(), w), dtype=self.torch.uint8,
                                  device=self.device)
-        self._elem_call(kind, _ELEM[kind].split, w, C.c_void_p(x.data_ptr()), x.numel(), C.c_void_p(image.data_ptr()),
-                        self._stream())
+        self._elem_call(kind, _ELEM[kind].split, w, C.c_void_p(x.data_ptr()), *b, x.numel(),
+                        C.c_void_p(image.data_ptr()), self._stream())
         return image
 
-    def _elem_merge(self, kind: str, image, n_elems: int, dtype):
-        """n_elems elements of `dtype` from an image."""
-        out = self.torch.empty(n_elems, dtype=dtype, device=self.device)
+    def _elem_merge(self, kind: str, image, n_elems: int, dtype, base=None, out=None):
+        """n_elems elements of `dtype` from an image (into `out` when given)."""
+        b = self._elem_base(kind, base, n_elems, dtype)
+        out = self._elem_out(out, n_elems, dtype)
         self._elem_call(kind, _ELEM[kind].merge, out.element_size(), C.c_void_p(image.data_ptr()), n_elems,
-                        C.c_void_p(out.data_ptr()), self._stream())
+                        C.c_void_p(out.data_ptr()), *b, self._stream())
         return out
 
-    def _elem_compress_into(self, kind: str, x, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+    def _elem_compress_into(self, kind: str, x, scratch, out, out_len, result, chunk_blocks: int = 0,
+                            base=None) -> None:
         """The compress call, no synchronisation: `scratch` a uint8 device
         tensor of >= the kind's scratch_bytes, `out` of >= its bound bytes (any
         alignment), `out_len` one int64, `result` two int32."""
         w = self._elem_width(kind, x)
+        b = self._elem_base(kind, base, x.numel(), x.dtype)
         p = self._frame_params(chunk_blocks)
-        self._elem_call(kind, "compress", C.byref(p), w, C.c_void_p(x.data_ptr()), x.numel(),
+        self._elem_call(kind, "compress", C.byref(p), w, C.c_void_p(x.data_ptr()), *b, x.numel(),
                         C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()), out.numel(),
                         C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()), self._stream())
 
-    def _elem_compress(self, kind: str, x, chunk_blocks: int = 0):
+    def _elem_compress(self, kind: str, x, chunk_blocks: int = 0, base=None):
         """Compress a contiguous device tensor of one of the kind's element
         widths into one frame of the kind: a uint8 device tensor of its exact
         length.  One synchronisation, to read the length."""
         t = self.torch
         w = self._elem_width(kind, x)
+        self._elem_base(kind, base, x.numel(), x.dtype)
         scratch = t.empty(self._elem_scratch_bytes(kind, x.numel(), w), dtype=t.uint8, device=self.device)
         out = t.empty(self._elem_bound(kind, x.numel(), w), dtype=t.uint8, device=self.device)
         out_len = t.zeros(1, dtype=t.int64, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self._elem_compress_into(kind, x, scratch, out, out_len, result, chunk_blocks)
+        self._elem_compress_into(kind, x, scratch, out, out_len, result, chunk_blocks, base)
         return out[: int(out_len.item())]
 
     @staticmethod
@@ -881,29 +921,32 @@ class BlockCodec:
             raise ValueError(f"dtype {dtype} has {w}-byte elements, the {kind} frame holds {info.elem_bytes}-byte ones")
 
     def _elem_decompress_into(self, kind: str, buf, info, inner: FrameInfo, scratch, out, block_status, result,
-                              chunk_blocks: int = 0) -> None:
+                              chunk_blocks: int = 0, base=None) -> None:
         """The decompress call, no synchronisation: `scratch` >= inner.n_total
-        bytes, `out` info.n_elems elements (16-byte aligned), `block_status`
-        inner.n_blocks int32 or None, `result` two int32."""
+        bytes, `out` info.n_elems elements (16-byte aligned; the base itself
+        for an in-place diff decode), `block_status` inner.n_blocks int32 or
+        None, `result` two int32."""
+        b = self._elem_base(kind, base, info.n_elems, out.dtype)
         self._elem_call(kind, "decompress", C.byref(info), C.byref(inner), chunk_blocks, C.c_void_p(buf.data_ptr()),
-                        buf.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()),
+                        buf.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(out.data_ptr()), *b,
                         out.numel() * out.element_size(),
                         C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
                         C.c_void_p(result.data_ptr()), self._stream())
 
-    def _elem_decompress(self, kind: str, buf, dtype, chunk_blocks: int = 0):
+    def _elem_decompress(self, kind: str, buf, dtype, chunk_blocks: int = 0, base=None, out=None):
         """Decode a frame of the kind (a uint8 device tensor) into a 1-D
-        tensor of `dtype`, whose size must be the frame's element width
-        (ValueError otherwise).  Returns (out, block_status); raises FseError
-        for a frame-level error (BAD_FRAME)."""
+        tensor of `dtype` (`out` when given), whose size must be the frame's
+        element width (ValueError otherwise).  Returns (out, block_status);
+        raises FseError for a frame-level error (BAD_FRAME)."""
         t = self.torch
         info, inner = self._elem_info(kind, buf)
         self._check_dtype(info, dtype, _ELEM[kind].label)
+        self._elem_base(kind, base, info.n_elems, dtype)
         scratch = t.empty(inner.n_total, dtype=t.uint8, device=self.device)
-        out = t.empty(info.n_elems, dtype=dtype, device=self.device)
+        out = self._elem_out(out, info.n_elems, dtype)
         status = t.zeros(inner.n_blocks, dtype=t.int32, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self._elem_decompress_into(kind, buf, info, inner, scratch, out, status, result, chunk_blocks)
+        self._elem_decompress_into(kind, buf, info, inner, scratch, out, status, result, chunk_blocks, base)
         check(int(result[0].item()), f"{_ELEM[kind].label} frame")
         return out, status
 
@@ -920,21 +963,23 @@ class BlockCodec:
         return int(self._elem_fn(kind, "ranges_scratch_bytes")(elem_bytes, arr, n))
 
     def _elem_decompress_ranges_into(self, kind: str, buf, info, inner: FrameInfo, ranges, scratch, out, range_status,
-                                     result, chunk_blocks: int = 0) -> None:
+                                     result, chunk_blocks: int = 0, base=None) -> None:
         """The decompress-ranges call, no synchronisation: `ranges` a sequence
         of (elem_off, n_elems, dst_elem_off) or what `planes_ranges` made of
         one; `scratch` >= the kind's ranges_scratch_bytes; range r goes to
         out[dst_elem_off: dst_elem_off + n_elems] (`out` of the frame's
-        element width, any alignment)."""
+        element width, any alignment; for a diff frame clear of `base`, the
+        whole base tensor)."""
         arr = ranges if isinstance(ranges, C.Array) else self.planes_ranges(ranges)
         n = 0 if getattr(arr, "empty", False) else len(arr)
+        b = self._elem_base(kind, base, info.n_elems, out.dtype)
         self._elem_call(kind, "decompress_ranges", C.byref(info), C.byref(inner), chunk_blocks,
                         C.c_void_p(buf.data_ptr()), buf.numel(), arr, n, C.c_void_p(scratch.data_ptr()),
-                        scratch.numel(), C.c_void_p(out.data_ptr()), out.numel() * out.element_size(),
+                        scratch.numel(), C.c_void_p(out.data_ptr()), *b, out.numel() * out.element_size(),
                         C.c_void_p(range_status.data_ptr()) if range_status is not None else None,
                         C.c_void_p(result.data_ptr()), self._stream())
 
-    def _elem_decompress_ranges(self, kind: str, buf, dtype, ranges, chunk_blocks: int = 0):
+    def _elem_decompress_ranges(self, kind: str, buf, dtype, ranges, chunk_blocks: int = 0, base=None):
         """Decode the element ranges [(elem_off, count), ...] of a frame of the
         kind without decoding the rest (a delta range from its restart group's
         first element on).  The ranges are packed back to back into one
@@ -944,6 +989,7 @@ class BlockCodec:
         t = self.torch
         info, inner = self._elem_info(kind, buf)
         self._check_dtype(info, dtype, _ELEM[kind].label)
+        self._elem_base(kind, base, info.n_elems, dtype)
         packed, at = [], 0
         for s, n in ranges:
             packed.append((s, n, at))
@@ -954,15 +1000,17 @@ class BlockCodec:
         out = t.empty(at, dtype=dtype, device=self.device)
         status = t.zeros(len(packed), dtype=t.int32, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self._elem_decompress_ranges_into(kind, buf, info, inner, arr, scratch, out, status, result, chunk_blocks)
+        self._elem_decompress_ranges_into(kind, buf, info, inner, arr, scratch, out, status, result, chunk_blocks,
+                                          base)
         check(int(result[0].item()), f"{_ELEM[kind].label} frame")
         return [out[d: d + n] for _, n, d in packed], status
 
-    def _elem_decompress_range(self, kind: str, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0):
+    def _elem_decompress_range(self, kind: str, buf, dtype, elem_off: int, count: int, chunk_blocks: int = 0,
+                               base=None):
         """Elements [elem_off, elem_off + count) of a frame of the kind as a
         tensor of `dtype`; raises FseError for a frame-level error or with the
         status of the first failed block the range needs."""
-        views, status = self._elem_decompress_ranges(kind, buf, dtype, [(elem_off, count)], chunk_blocks)
+        views, status = self._elem_decompress_ranges(kind, buf, dtype, [(elem_off, count)], chunk_blocks, base)
         check(int(status[0].item()), f"{_ELEM[kind].label} frame range")
         return views[0]
 
@@ -1080,6 +1128,80 @@ class BlockCodec:
         """`_elem_decompress_range` of a delta frame: one tensor."""
         return self._elem_decompress_range("delta", buf, dtype, elem_off, count, chunk_blocks)
 
+    # the diff frame's names (1-, 2-, 4- and 8-byte elements): `base` is a
+    # contiguous device tensor of the dtype and element count of `x` (decode:
+    # of the header), ValueError otherwise; the decoded dtype is the base's.
+    # Passing out=base decodes in place.
+    @staticmethod
+    def _diff_base(base):
+        if base is None or not hasattr(base, "data_ptr"):
+            raise ValueError("the diff frame needs its base tensor")
+        return base
+
+    def diff_bound(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_diff_bound`: a capacity no diff frame of n_elems elements exceeds."""
+        return self._elem_bound("diff", n_elems, elem_bytes)
+
+    def diff_scratch_bytes(self, n_elems: int, elem_bytes: int) -> int:
+        """`fsehip_diff_scratch_bytes`: the diff image's bytes."""
+        return self._elem_scratch_bytes("diff", n_elems, elem_bytes)
+
+    def diff_encode(self, x, base):
+        """`fsehip_diff_encode`: `_elem_split` for the diff image of `x` against `base`."""
+        return self._elem_split("diff", x, base)
+
+    def diff_decode(self, image, base, out=None):
+        """`fsehip_diff_decode`: `_elem_merge` from a diff image against
+        `base`, into a fresh tensor, `out`, or the base itself (out=base)."""
+        base = self._diff_base(base)
+        return self._elem_merge("diff", image, base.numel(), base.dtype, base, out)
+
+    def compress_diff_into(self, x, base, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_diff_compress`: `_elem_compress_into` for a diff frame."""
+        self._elem_compress_into("diff", x, scratch, out, out_len, result, chunk_blocks, base)
+
+    def compress_diff(self, x, base, chunk_blocks: int = 0):
+        """`_elem_compress` into one diff frame of `x` against `base`."""
+        return self._elem_compress("diff", x, chunk_blocks, base)
+
+    @staticmethod
+    def diff_info(buf):
+        """`fsehip_diff_read_header`: `_elem_info`, (DiffInfo, FrameInfo)."""
+        return BlockCodec._elem_info("diff", buf)
+
+    def decompress_diff_into(self, buf, info: DiffInfo, inner: FrameInfo, base, scratch, out, block_status, result,
+                             chunk_blocks: int = 0) -> None:
+        """`fsehip_diff_decompress`: `_elem_decompress_into` for a diff frame (out may be the base)."""
+        self._elem_decompress_into("diff", buf, info, inner, scratch, out, block_status, result, chunk_blocks, base)
+
+    def decompress_diff(self, buf, base, out=None, chunk_blocks: int = 0):
+        """`_elem_decompress` of a diff frame against `base`: (out,
+        block_status), out of the base's dtype; out=base updates the base
+        where it lies.  The frame does not identify its base: another one
+        decodes to other values with every status OK (compress_sealed(kind=
+        "diff") adds checksums that tell)."""
+        return self._elem_decompress("diff", buf, self._diff_base(base).dtype, chunk_blocks, base, out)
+
+    def diff_ranges_scratch_bytes(self, elem_bytes: int, ranges) -> int:
+        """`fsehip_diff_ranges_scratch_bytes` for a sequence of triples or a `planes_ranges` array."""
+        return self._elem_ranges_scratch_bytes("diff", elem_bytes, ranges)
+
+    def decompress_diff_ranges_into(self, buf, info: DiffInfo, inner: FrameInfo, ranges, base, scratch, out,
+                                    range_status, result, chunk_blocks: int = 0) -> None:
+        """`fsehip_diff_decompress_ranges`: `_elem_decompress_ranges_into` for
+        a diff frame; `base` is the whole base tensor and `out` lies clear of it."""
+        self._elem_decompress_ranges_into("diff", buf, info, inner, ranges, scratch, out, range_status, result,
+                                          chunk_blocks, base)
+
+    def decompress_diff_ranges(self, buf, base, ranges, chunk_blocks: int = 0):
+        """`_elem_decompress_ranges` of a diff frame against the whole base: (views, range statuses)."""
+        return self._elem_decompress_ranges("diff", buf, self._diff_base(base).dtype, ranges, chunk_blocks, base)
+
+    def decompress_diff_range(self, buf, base, elem_off: int, count: int, chunk_blocks: int = 0):
+        """`_elem_decompress_range` of a diff frame against the whole base: one tensor."""
+        return self._elem_decompress_range("diff", buf, self._diff_base(base).dtype, elem_off, count, chunk_blocks,
+                                           base)
+
     # ------------------------------------------------------------ the check record and sealed buffers
     # fsehip.h section 2f: a CRC-32 (zlib's) per check block of the content,
     # in a record of its own in front of an unchanged container.
@@ -1177,7 +1299,7 @@ class BlockCodec:
                 raise ValueError("a sealed frame takes a 1-byte tensor; wider elements go to kind='planes' or 'delta'")
             return 1
         if kind not in _ELEM:
-            raise ValueError(f"kind {kind!r}: 'frame', 'planes' or 'delta'")
+            raise ValueError(f"kind {kind!r}: 'frame', 'planes', 'delta' or 'diff'")
         return self._elem_width(kind, x)
 
     def sealed_bound(self, x, kind: str = "frame", check_block: int = 65536) -> int:
@@ -1187,26 +1309,32 @@ class BlockCodec:
         return self.check_bytes(self._content_bytes(x), check_block) + inner
 
     def compress_sealed_into(self, x, kind, buf, out_len, result, scratch=None, check_block: int = 65536,
-                             chunk_blocks: int = 0) -> int:
+                             chunk_blocks: int = 0, base=None) -> int:
         """The record of `x` at buf[0], then the existing compress_*_into
         straight to the record's end: no synchronisation, no copy of the
         container.  `buf` >= sealed_bound bytes, `out_len` one int64 (the
-        CONTAINER's length), `result` two int32, `scratch` as the plane or
-        delta call's.  Returns the record's size: the buffer's length is that
-        plus out_len."""
+        CONTAINER's length), `result` two int32, `scratch` as the plane,
+        delta or diff call's, `base` for kind 'diff' alone.  Returns the
+        record's size: the buffer's length is that plus out_len."""
         self._sealed_kind(x, kind)
+        if kind == "frame":
+            if base is not None:
+                raise ValueError("a sealed frame takes no base")
+        else:
+            self._elem_base(kind, base, x.numel(), x.dtype)
         rec = self.check_bytes(self._content_bytes(x), check_block)
         self.check_build_into(x, buf[:rec], check_block)
         if kind == "frame":
             self.compress_frame_into(x, buf[rec:], out_len, result, chunk_blocks)
         else:
-            self._elem_compress_into(kind, x, scratch, buf[rec:], out_len, result, chunk_blocks)
+            self._elem_compress_into(kind, x, scratch, buf[rec:], out_len, result, chunk_blocks, base)
         return rec
 
-    def compress_sealed(self, x, kind: str = "frame", check_block: int = 65536, chunk_blocks: int = 0):
+    def compress_sealed(self, x, kind: str = "frame", check_block: int = 65536, chunk_blocks: int = 0, base=None):
         """Compress a contiguous device tensor into one sealed buffer (a check
-        record, then a frame, plane frame or delta frame): a uint8 device
-        tensor of its exact length.  One synchronisation, to read the length."""
+        record, then a frame, plane frame, delta frame or -- kind 'diff',
+        against `base` -- diff frame): a uint8 device tensor of its exact
+        length.  One synchronisation, to read the length."""
         t = self.torch
         w = self._sealed_kind(x, kind)
         scratch = None
@@ -1215,7 +1343,7 @@ class BlockCodec:
         buf = t.empty(self.sealed_bound(x, kind, check_block), dtype=t.uint8, device=self.device)
         out_len = t.zeros(1, dtype=t.int64, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        rec = self.compress_sealed_into(x, kind, buf, out_len, result, scratch, check_block, chunk_blocks)
+        rec = self.compress_sealed_into(x, kind, buf, out_len, result, scratch, check_block, chunk_blocks, base)
         return buf[: rec + int(out_len.item())]
 
     @staticmethod
@@ -1223,7 +1351,7 @@ class BlockCodec:
         """`fsehip_sealed_read_header` of a sealed buffer given as bytes, a
         numpy array or a tensor (the record and the container's first 48 bytes
         come to the host): (CheckInfo, kind, inner_off) with kind 'frame',
-        'planes' or 'delta' and the container at buf[inner_off:]; raises
+        'planes', 'delta' or 'diff' and the container at buf[inner_off:]; raises
         FseError (BAD_FRAME) otherwise."""
         info = BlockCodec.check_info(buf)
         upto = 32 + 4 * info.n_cb + 48
@@ -1254,31 +1382,46 @@ class BlockCodec:
         return self.frame_info(inner) if kind == "frame" else self._elem_info(kind, inner)
 
     def decompress_sealed_into(self, buf, sealed, inner_info, out, block_status, result, check_status, check_result,
-                               scratch=None, chunk_blocks: int = 0) -> None:
+                               scratch=None, chunk_blocks: int = 0, base=None) -> None:
         """The existing decompress_*_into of the container, then
         `fsehip_check_verify` on the output; no synchronisation.  `sealed` is
         what sealed_info gave for the buffer, `inner_info` what
         sealed_inner_info gave for its container; `out`, `block_status`,
-        `result` and `scratch` as the container's call, `check_status`
-        sealed[0].n_cb int32, `check_result` two int32."""
+        `result`, `scratch` and `base` (a diff frame's) as the container's
+        call, `check_status` sealed[0].n_cb int32, `check_result` two int32."""
         info, kind, off = sealed
         inner = buf[off:]
         if kind == "frame":
             self.decompress_frame_into(inner, inner_info, out, block_status, result, chunk_blocks)
         else:
-            self._elem_decompress_into(kind, inner, *inner_info, scratch, out, block_status, result, chunk_blocks)
+            self._elem_decompress_into(kind, inner, *inner_info, scratch, out, block_status, result, chunk_blocks,
+                                       base)
         self.check_verify_into(buf, info, out, check_status, check_result)
 
-    def decompress_sealed(self, buf, dtype=None, chunk_blocks: int = 0, with_result: bool = False):
+    def _sealed_base(self, kind: str, base, dtype):
+        """`base` belongs to a sealed diff buffer and to no other; its dtype is
+        the default one there.  Returns the dtype to decode to."""
+        if kind == "diff":
+            if base is None:
+                raise ValueError("a sealed diff buffer needs base=")
+            return dtype or self._diff_base(base).dtype
+        if base is not None:
+            raise ValueError(f"a sealed {kind} buffer takes no base")
+        return dtype
+
+    def decompress_sealed(self, buf, dtype=None, chunk_blocks: int = 0, with_result: bool = False, base=None):
         """Decode a sealed buffer (a uint8 device tensor) with the existing
         decompress of its container, then verify the output against the
         record: (out, block_status, check_status), or with_result=True
         (out, block_status, check_status, result) with the verify's two int32
         (result[0]: OK, CHECKSUM of the whole content; result[1]: failed check
-        blocks).  Raises FseError for a buffer-level error (BAD_FRAME)."""
+        blocks).  A sealed diff buffer needs `base` (dtype defaults to the
+        base's), and a wrong base shows as CHECKSUM in the check blocks it
+        changes.  Raises FseError for a buffer-level error (BAD_FRAME)."""
         t = self.torch
         sealed = info, kind, off = self.sealed_info(buf)
         inner_info = self.sealed_inner_info(kind, buf[off:])
+        dtype = self._sealed_base(kind, base, dtype)
         dt = self._sealed_dtype(kind, buf[off:], dtype)
         scratch = None
         if kind == "frame":
@@ -1286,6 +1429,7 @@ class BlockCodec:
             out = t.empty(info.n_content, dtype=dt, device=self.device)
         else:
             self._check_dtype(inner_info[0], dt, _ELEM[kind].label)
+            self._elem_base(kind, base, inner_info[0].n_elems, dt)
             finfo = inner_info[1]
             scratch = t.empty(finfo.n_total, dtype=t.uint8, device=self.device)
             out = t.empty(inner_info[0].n_elems, dtype=dt, device=self.device)
@@ -1294,7 +1438,7 @@ class BlockCodec:
         check_status = t.zeros(info.n_cb, dtype=t.int32, device=self.device)
         check_result = t.zeros(2, dtype=t.int32, device=self.device)
         self.decompress_sealed_into(buf, sealed, inner_info, out, block_status, result, check_status, check_result,
-                                    scratch, chunk_blocks)
+                                    scratch, chunk_blocks, base)
         check(int(result[0].item()), f"sealed {kind}")
         if int(check_result[0].item()) == -19:  # the record on the device is not the one the host read
             raise FseError(-19, "check record")
@@ -1302,10 +1446,11 @@ class BlockCodec:
             return out, block_status, check_status, check_result
         return out, block_status, check_status
 
-    def decompress_sealed_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0):
+    def decompress_sealed_ranges(self, buf, dtype, ranges, chunk_blocks: int = 0, base=None):
         """Decode the ranges [(off, count), ...] of a sealed buffer without
-        decoding the rest -- elements of `dtype` when the container is a plane
-        or delta frame, bytes (dtype None or a 1-byte one) for a frame -- and
+        decoding the rest -- elements of `dtype` when the container is a plane,
+        delta or diff frame (the last against `base`, the whole base tensor),
+        bytes (dtype None or a 1-byte one) for a frame -- and
         verify the check blocks each range wholly covers.  Returns (views, one
         per range, of one packed tensor; the container's range statuses; the
         check's range statuses, OK or CHECKSUM).  Raises FseError for a
@@ -1313,7 +1458,7 @@ class BlockCodec:
         t = self.torch
         info, kind, off = self.sealed_info(buf)
         inner = buf[off:]
-        dt = self._sealed_dtype(kind, inner, dtype)
+        dt = self._sealed_dtype(kind, inner, self._sealed_base(kind, base, dtype))
         w = t.empty(0, dtype=dt).element_size()
         packed, at = [], 0
         for s, n in ranges:
@@ -1330,7 +1475,7 @@ class BlockCodec:
             arr = self.planes_ranges(packed)
             scratch = t.empty(max(self._elem_ranges_scratch_bytes(kind, w, arr), 16), dtype=t.uint8, device=self.device)
             self._elem_decompress_ranges_into(kind, inner, pinfo, finfo, arr, scratch, out, status, result,
-                                              chunk_blocks)
+                                              chunk_blocks, base)
         check(int(result[0].item()), f"sealed {kind}")
         check_status = t.zeros(len(packed), dtype=t.int32, device=self.device)
         check_result = t.zeros(2, dtype=t.int32, device=self.device)
@@ -1339,12 +1484,12 @@ class BlockCodec:
         check(int(check_result[0].item()), "check record")
         return [out[d: d + n] for _, n, d in packed], status, check_status
 
-    def decompress_sealed_range(self, buf, dtype, off: int, count: int, chunk_blocks: int = 0):
+    def decompress_sealed_range(self, buf, dtype, off: int, count: int, chunk_blocks: int = 0, base=None):
         """One range of a sealed buffer as a tensor; raises FseError for a
         buffer-level error, with the status of the first failed block the
         range touches, or with CHECKSUM when a check block the range wholly
         covers fails."""
-        views, status, check_status = self.decompress_sealed_ranges(buf, dtype, [(off, count)], chunk_blocks)
+        views, status, check_status = self.decompress_sealed_ranges(buf, dtype, [(off, count)], chunk_blocks, base)
         check(int(status[0].item()), "sealed range")
         check(int(check_status[0].item()), "sealed range")
         return views[0]
@@ -1464,15 +1609,18 @@ class BlockCodec:
             return self.compress_frame(raw, chunk_blocks), kind
         return self._elem_compress(kind, x, chunk_blocks), kind
 
-    def decompress_auto(self, buf, dtype, chunk_blocks: int = 0):
-        """Decode a frame, plane frame or delta frame (a uint8 device tensor)
-        by its magic into a 1-D tensor of `dtype`: (out, block_status) as
-        decompress_frame / decompress_planes / decompress_delta.  A frame's
-        bytes are viewed as `dtype` (ValueError when they are no whole number
-        of elements)."""
+    def decompress_auto(self, buf, dtype, chunk_blocks: int = 0, base=None):
+        """Decode a frame, plane frame, delta frame or diff frame (a uint8
+        device tensor) by its magic into a 1-D tensor of `dtype`: (out,
+        block_status) as decompress_frame / decompress_planes /
+        decompress_delta / decompress_diff.  A frame's bytes are viewed as
+        `dtype` (ValueError when they are no whole number of elements).  A
+        diff frame needs `base` (ValueError without); the others ignore it."""
         kind = container_kind(buf)
+        if kind == "diff" and base is None:
+            raise ValueError("a diff frame decodes against its base: pass base=")
         if kind in _ELEM:
-            return self._elem_decompress(kind, buf, dtype, chunk_blocks)
+            return self._elem_decompress(kind, buf, dtype, chunk_blocks, base if kind == "diff" else None)
         if kind != "frame":
             raise ValueError("a sealed buffer goes to decompress_sealed")
         out, status = self.decompress_frame(buf, chunk_blocks)
@@ -1535,7 +1683,18 @@ def frame_decompress_range(data, offset: int, length: int, device=None) -> bytes
 _INT_VIEW = {1: np.uint8, 2: np.int16, 4: np.int32, 8: np.int64}
 
 
-def _elem_compress(kind: str, data, block_size: int, table_log: int, ckpt_interval: int, nstates: int, device) -> bytes:
+def _host_base(a: np.ndarray, base) -> np.ndarray:
+    """A diff frame's base on the host: an array of a's dtype and element count (ValueError otherwise)."""
+    if base is None:
+        raise ValueError("the diff frame needs its base array")
+    b = np.ascontiguousarray(base)
+    if b.dtype != a.dtype or b.size != a.size:
+        raise ValueError(f"base has {b.size} items of {b.dtype}, the array {a.size} of {a.dtype}")
+    return b.reshape(-1).view(_INT_VIEW[b.dtype.itemsize])
+
+
+def _elem_compress(kind: str, data, block_size: int, table_log: int, ckpt_interval: int, nstates: int, device,
+                   base=None) -> bytes:
     """Compress a numpy array of one of the kind's item sizes into one frame
     of the kind on the GPU; copies through torch.  The element width is
     stored, the dtype and the shape are not."""
@@ -1547,10 +1706,11 @@ def _elem_compress(kind: str, data, block_size: int, table_log: int, ckpt_interv
     codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
                        nstates=nstates)
     src = torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device)
-    return codec._elem_compress(kind, src).cpu().numpy().tobytes()
+    dbase = torch.from_numpy(_host_base(a, base).copy()).to(codec.device) if _ELEM[kind].based else None
+    return codec._elem_compress(kind, src, 0, dbase).cpu().numpy().tobytes()
 
 
-def _elem_decompress(kind: str, data, dtype, device) -> np.ndarray:
+def _elem_decompress(kind: str, data, dtype, device, base=None) -> np.ndarray:
     """Decode a frame of the kind held in host memory into a 1-D numpy array
     of `dtype` (its item size must be the frame's element width); raises
     FseError on a frame-level error or with the first failed block's status."""
@@ -1562,7 +1722,11 @@ def _elem_decompress(kind: str, data, dtype, device) -> np.ndarray:
     if dt.itemsize != info.elem_bytes:
         raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the {label} frame holds {info.elem_bytes}-byte ones")
     buf = torch.from_numpy(_buf(data).copy()).to(codec.device)
-    out, status = codec._elem_decompress(kind, buf, getattr(torch, np.dtype(_INT_VIEW[info.elem_bytes]).name))
+    dbase = None
+    if _ELEM[kind].based:
+        dbase = torch.from_numpy(_host_base(np.empty(info.n_elems, dtype=dt), base).copy()).to(codec.device)
+    out, status = codec._elem_decompress(kind, buf, getattr(torch, np.dtype(_INT_VIEW[info.elem_bytes]).name), 0,
+                                         dbase)
     st = status.cpu().numpy()
     if st.any():
         b = int(np.flatnonzero(st)[0])
@@ -1592,6 +1756,22 @@ def delta_decompress(data, dtype, device=None) -> np.ndarray:
     return _elem_decompress("delta", data, dtype, device)
 
 
+def diff_compress(data, base, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2,
+                  device=None) -> bytes:
+    """`_elem_compress` of a numpy array of item size 1, 2, 4 or 8 against a
+    base array of its dtype and size into one diff frame (fsehip.h section 2h)."""
+    return _elem_compress("diff", data, block_size, table_log, ckpt_interval, nstates, device, base)
+
+
+def diff_decompress(data, base, device=None) -> np.ndarray:
+    """`_elem_decompress` of a diff frame held in host memory against `base`,
+    a numpy array of the frame's element count; the result has its dtype.
+    The frame does not identify its base: see BlockCodec.decompress_diff."""
+    if base is None:
+        raise ValueError("the diff frame needs its base array")
+    return _elem_decompress("diff", data, np.asarray(base).dtype, device, base)
+
+
 # ---------------------------------------------------------------- the size estimate and the automatic choice
 def log2q8(c: int) -> int:
     """`fsehip_log2q8`: the estimate's 256 * log2(c) for 1 <= c <= 32768 (host, no device)."""
@@ -1615,7 +1795,7 @@ def estimate_choose(est):
 
 
 def container_kind(buf) -> str:
-    """`fsehip_container_kind`: "frame", "planes", "delta" or "sealed" from
+    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed" or "diff" from
     the magic of a container given as bytes, a numpy array or a tensor (its
     first 4 bytes come to the host); raises FseError (BAD_FRAME) for anything
     else."""
@@ -1627,7 +1807,7 @@ def container_kind(buf) -> str:
     k = load().fsehip_container_kind(_p(a), len(a))
     if k < 0:
         raise FseError(k, "fsehip_container_kind")
-    return "sealed" if k == KIND_SEALED else KINDS[k]
+    return "sealed" if k == KIND_SEALED else "diff" if k == KIND_DIFF else KINDS[k]
 
 
 def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
@@ -1648,13 +1828,16 @@ def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0,
     return buf.cpu().numpy().tobytes(), kind
 
 
-def auto_decompress(blob, dtype, device=None) -> np.ndarray:
-    """Decode what auto_compress returned, by its magic, into a 1-D numpy
+def auto_decompress(blob, dtype, device=None, base=None) -> np.ndarray:
+    """Decode what auto_compress returned -- or a diff frame, with its base
+    array as `base` (ValueError without) -- by its magic, into a 1-D numpy
     array of `dtype`; raises FseError as frame_decompress / planes_decompress
-    / delta_decompress."""
+    / delta_decompress / diff_decompress."""
     kind = container_kind(_buf(blob))
+    if kind == "diff" and base is None:
+        raise ValueError("a diff frame decodes against its base: pass base=")
     if kind in _ELEM:
-        return _elem_decompress(kind, blob, dtype, device)
+        return _elem_decompress(kind, blob, dtype, device, base if kind == "diff" else None)
     if kind != "frame":
         raise ValueError("a sealed buffer goes to sealed_decompress")
     return np.frombuffer(frame_decompress(blob, device), dtype=np.dtype(dtype))
@@ -1673,10 +1856,11 @@ def crc32_combine(crc1: int, crc2: int, len2: int) -> int:
 
 
 def sealed_compress(data, kind: str = "frame", check_block: int = 65536, block_size: int = 65536, table_log: int = 0,
-                    ckpt_interval: int = 128, nstates: int = 2, device=None) -> bytes:
+                    ckpt_interval: int = 128, nstates: int = 2, device=None, base=None) -> bytes:
     """Compress a host buffer into one sealed buffer (fsehip.h section 2f) on
     the GPU: bytes or any numpy array for kind 'frame', a numpy array of item
-    size 2, 4 or 8 for 'planes' and of 1, 2, 4 or 8 for 'delta'."""
+    size 2, 4 or 8 for 'planes' and of 1, 2, 4 or 8 for 'delta' and for
+    'diff', which codes it against `base`, an array of its dtype and size."""
     import torch
 
     codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
@@ -1687,15 +1871,19 @@ def sealed_compress(data, kind: str = "frame", check_block: int = 65536, block_s
         a = np.ascontiguousarray(data)
         if a.dtype.itemsize not in _INT_VIEW:
             raise ValueError(f"item size {a.dtype.itemsize}: 1, 2, 4 or 8 bytes")
+        if kind == "diff":
+            base = torch.from_numpy(_host_base(a, base).copy()).to(codec.device)
         a = a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize])
     src = torch.from_numpy(a.copy()).to(codec.device)
-    return codec.compress_sealed(src, kind, check_block).cpu().numpy().tobytes()
+    return codec.compress_sealed(src, kind, check_block, base=base).cpu().numpy().tobytes()
 
 
-def sealed_decompress(blob, dtype=None, device=None):
+def sealed_decompress(blob, dtype=None, device=None, base=None):
     """Decode a sealed buffer held in host memory: bytes for a sealed frame, a
     1-D numpy array of `dtype` (default: the integer of the element width) for
-    a plane or delta frame.  Raises FseError on a buffer-level error
+    a plane, delta or diff frame; the last needs `base`, an array of the
+    frame's element count and width, and a wrong one raises CHECKSUM.  Raises
+    FseError on a buffer-level error
     (BAD_FRAME), with the first failed block's status, and with CHECKSUM when
     a check block or the whole content's CRC-32 fails."""
     import torch
@@ -1704,7 +1892,15 @@ def sealed_decompress(blob, dtype=None, device=None):
     info, kind, off = BlockCodec.sealed_info(_buf(blob))  # not a sealed buffer: BAD_FRAME before any device work
     buf = torch.from_numpy(_buf(blob).copy()).to(codec.device)
     dt = None if dtype is None else np.dtype(dtype)
-    out, status, check_status, result = codec.decompress_sealed(buf, None, with_result=True)
+    dbase = None
+    if kind == "diff":
+        if base is None:
+            raise ValueError("a sealed diff buffer needs base=")
+        b = np.ascontiguousarray(base).reshape(-1)
+        if b.dtype.itemsize not in _INT_VIEW:
+            raise ValueError(f"item size {b.dtype.itemsize}: 1, 2, 4 or 8 bytes")
+        dbase = torch.from_numpy(b.view(_INT_VIEW[b.dtype.itemsize]).copy()).to(codec.device)
+    out, status, check_status, result = codec.decompress_sealed(buf, None, with_result=True, base=dbase)
     if dt is not None and dt.itemsize != out.element_size():
         raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, the sealed buffer holds {out.element_size()}-byte ones")
     st = status.cpu().numpy()
@@ -1868,6 +2064,7 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "encode_table_new", "frame_compress", "frame_decompress", "frame_decompress_range",
            "histogram_count", "histogram_new", "norm_histogram_new", "norm_histogram_read", "norm_histogram_write",
            "normalize", "normalize_optimal", "SharedTable", "norm_histogram_try_from",
-           "planes_compress", "planes_decompress", "delta_compress", "delta_decompress",
+           "planes_compress", "planes_decompress", "delta_compress", "delta_decompress", "diff_compress",
+           "diff_decompress",
            "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo",
            "auto_compress", "auto_decompress", "container_kind", "estimate_choose", "log2q8"]

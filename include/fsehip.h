@@ -1082,7 +1082,7 @@ int fsehip_delta_decompress_ranges(const fsehip_delta_info* info, const fsehip_f
  * (0.006 % at 16, 1.6 % at 8).
  *
  * A SEALED BUFFER is a check record followed directly by exactly one
- * container of section 2b, 2d or 2e; the container's magic says which.  The
+ * container of section 2b, 2d, 2e or 2h; the container's magic says which.  The
  * container's content length (n_total; n_elems * w) must equal n_content and
  * the buffer ends with the container: anything else is BAD_FRAME.  The
  * record's size is known before anything runs, so the container is
@@ -1094,6 +1094,7 @@ int fsehip_delta_decompress_ranges(const fsehip_delta_info* info, const fsehip_f
 #define FSEHIP_SEALED_FRAME 0u  /* `kind` of fsehip_sealed_read_header */
 #define FSEHIP_SEALED_PLANES 1u
 #define FSEHIP_SEALED_DELTA 2u
+#define FSEHIP_SEALED_DIFF 3u   /* a diff frame (section 2h): decoding needs the base */
 
 typedef struct {
     uint32_t version, algorithm, check_log, reserved; /* reserved: byte 7 | the word at 24 */
@@ -1124,8 +1125,8 @@ int fsehip_check_read_header(const uint8_t* hdr, size_t len, fsehip_check_info* 
  * fields would not pass fsehip_check_read_header. */
 int fsehip_check_write_header(const fsehip_check_info* info, uint8_t hdr[32]);
 /* The head of a sealed buffer (host pointer; len = bytes available, at least
- * the record and the first 32 bytes of a frame or 48 of a plane or delta
- * frame): the record's header into `info`, the container's kind from its
+ * the record and the first 32 bytes of a frame or 48 of a plane, delta or
+ * diff frame): the record's header into `info`, the container's kind from its
  * magic, and *inner_off = 32 + 4 * n_cb, where the container starts.
  * BAD_FRAME for a record fsehip_check_read_header rejects, a head too short,
  * another magic, or a container whose content length is not n_content.  The
@@ -1243,6 +1244,7 @@ int fsehip_check_verify_ranges(const fsehip_check_info* info, const uint8_t* d_r
 #define FSEHIP_KIND_PLANES 1u /* section 2d, magic "FSEP" */
 #define FSEHIP_KIND_DELTA 2u  /* section 2e, magic "FSED" */
 #define FSEHIP_KIND_SEALED 3u /* section 2f, magic "FSEK": fsehip_container_kind only */
+#define FSEHIP_KIND_DIFF 4u   /* section 2h, magic "FSEB": fsehip_container_kind only; no estimate */
 #define FSEHIP_EST_NONE UINT64_MAX /* an estimate that was not asked for or does not exist */
 #define FSEHIP_EST_RAW 0u /* block types, the frame directory's */
 #define FSEHIP_EST_RLE 1u
@@ -1269,7 +1271,8 @@ typedef struct {
  *    count whose norm entry is 0 or above 2^norm_log.
  *  fsehip_container_kind: the FSEHIP_KIND_* value of a buffer's magic (host
  *    pointer, len = bytes available; a sealed buffer reports
- *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's),
+ *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's;
+ *    a diff frame of section 2h FSEHIP_KIND_DIFF, which no estimate call takes),
  *    FSE_ERR_BAD_FRAME for len < 4 or any other magic, BAD_ARG for a null buf
  *    with len > 0.  Only the magic is read; the headers have their readers. */
 uint32_t fsehip_log2q8(uint32_t c);
@@ -1348,6 +1351,147 @@ uint64_t fsehip_estimate_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes, ui
 int fsehip_estimate(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t elem_bytes, const void* d_src,
                     uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes, uint64_t* d_est,
                     fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * (2h) The diff frame: a tensor coded as its difference against a base tensor
+ *
+ * The tensors moved most often are versions of something the receiver already
+ * holds: a checkpoint beside the previous one, weights after an optimiser
+ * step, a fine-tune beside its base, a table with a few rows replaced.  The
+ * diff frame codes the zigzag differences of the elements' bit patterns
+ * against the base tensor's, split into byte planes, with one unchanged frame
+ * of section 2b.  This library's own container, version 1; integers
+ * little-endian, any byte address:
+ *
+ *    0  u8[4] magic "FSEB"   ("against a base")
+ *    4  u8    version = 1
+ *    5  u8    elem_bytes w: 1, 2, 4 or 8
+ *    6  u16   reserved = 0
+ *    8  u64   n_elems
+ *   16  one frame (section 2b) of the diff image, to the end of the buffer
+ *
+ * Diff image: the elements of the tensor x and of the base b, n_elems each,
+ * are read as unsigned little-endian integers of w bytes, whatever the dtype,
+ * and all arithmetic is mod 2^(8 w).
+ *   d_i = x_i - b_i;
+ *   z_i = (d_i << 1) ^ (0 - (d_i >> (8 w - 1)))            (zigzag);
+ *   image[k * stride + i] = byte k of z_i, k < w, i < n_elems,
+ * with stride = roundup(n_elems, 16) and the stride - n_elems pad bytes of
+ * each plane zero: for w = 2, 4, 8 the plane image (section 2d) of z, for
+ * w = 1 z itself, padded.  The inner frame's n_total must equal w * stride.
+ * Decode: d_i = (z_i >> 1) ^ (0 - (z_i & 1)), x_i = b_i + d_i.  There are no
+ * restarts: an element depends on its own base element only, so an element
+ * range needs its own bytes of each plane and its own base elements, nothing
+ * else.  n_elems = 0 is valid: 16 + 32 bytes.  There is one format: subtract
+ * and zigzag, no XOR variant and no mode field (DESIGN.md section 5 "Diff").
+ *
+ * THE CONTAINER DOES NOT IDENTIFY THE BASE.  Decoding against another base
+ * gives other bytes with every status FSE_OK.  The guard is the sealed buffer
+ * of section 2f: its CRCs are taken over the content, so a wrong base is
+ * reported as CHECKSUM for each check block it changes.  "FSEB" is BAD_FRAME
+ * to the readers of sections 2b, 2d and 2e, and their magics are BAD_FRAME to
+ * this one.
+ *
+ * The calls mirror section 2d's call for call, with the base, a device
+ * pointer to n_elems elements aligned to elem_bytes, after the source or
+ * destination pointer.  Their argument rules are the plane calls', and,
+ * before any device use: a null d_base with n_elems > 0, or one not aligned
+ * to elem_bytes, is BAD_ARG.  The encode side only reads: d_src == d_base is
+ * fine (and codes all zeros).
+ *
+ * IN-PLACE DECODE: fsehip_diff_decode and fsehip_diff_decompress allow d_out
+ * == d_base (d_dst == d_base) and then update the base where it lies; any
+ * other overlap of [d_out, d_out + n_elems * w) with [d_base, d_base + n_elems
+ * * w) is BAD_ARG.  What an in-place decode leaves behind: on BAD_FRAME the
+ * base is untouched; after a failed inner block the elements with a byte in
+ * that block are undefined -- exactly as out of place, but now the base's
+ * values there are gone too.  A caller who cannot lose the base decodes out
+ * of place.  fsehip_diff_decompress_ranges allows no overlap of the
+ * destinations' extent with the base at all: BAD_ARG.
+ * ------------------------------------------------------------------------ */
+
+typedef fsehip_planes_info fsehip_diff_info; /* the same fields (section 2d) */
+
+/* 16 + fsehip_frame_bound(w * stride, block_size): a capacity no diff frame
+ * of n_elems elements exceeds (the inner frame's RAW fallback bounds it
+ * whatever the base).  0 for elem_bytes outside {1, 2, 4, 8} or when a size
+ * overflows 64 bits. */
+uint64_t fsehip_diff_bound(uint64_t n_elems, uint32_t elem_bytes, uint32_t block_size);
+/* w * stride, the diff image's bytes: the scratch of fsehip_diff_compress /
+ * fsehip_diff_decompress and the destination of fsehip_diff_encode.  0 for a
+ * bad elem_bytes or on overflow (and for n_elems = 0). */
+uint64_t fsehip_diff_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes);
+/* Parse and validate the first 48 bytes of a diff frame (host pointer; len =
+ * bytes available), as fsehip_planes_read_header: BAD_FRAME for len < 48, bad
+ * magic or version, elem_bytes outside {1, 2, 4, 8}, a nonzero reserved
+ * field, w * stride overflowing, an inner header fsehip_frame_read_header
+ * rejects, or an inner n_total other than w * stride.  Outputs are zeroed on
+ * every reject. */
+int fsehip_diff_read_header(const uint8_t* hdr, size_t len, fsehip_diff_info* out, fsehip_frame_info* inner);
+/* The 16 header bytes of `info` (stride and pad_ are not stored); BAD_ARG when
+ * the fields would not pass fsehip_diff_read_header. */
+int fsehip_diff_write_header(const fsehip_diff_info* info, uint8_t hdr[16]);
+
+/* The bare transforms, asynchronous on `stream`.
+ *  fsehip_diff_encode: n_elems elements of elem_bytes at d_src against those
+ *    at d_base -> the diff image at d_dst (fsehip_diff_scratch_bytes, 16-byte
+ *    aligned), pads zeroed.  d_src and d_base need only be aligned to
+ *    elem_bytes, each on its own; reads of either go up to roundup(n_elems *
+ *    elem_bytes, 4) at most.
+ *  fsehip_diff_decode: the diff image at d_src (16-byte aligned) and the base
+ *    -> exactly the n_elems * elem_bytes bytes at d_dst (16-byte aligned;
+ *    d_base itself or clear of it).  Reads of d_base go up to roundup(n_elems
+ *    * elem_bytes, 4) at most.
+ * BAD_ARG (a null or misaligned pointer with n_elems > 0; a destination that
+ * overlaps the base without being it), UNSUPPORTED (elem_bytes outside {1, 2,
+ * 4, 8}; w * stride overflowing) and NO_DEVICE before any device use.
+ * n_elems == 0 returns FSE_OK and does nothing. */
+int fsehip_diff_encode(uint32_t elem_bytes, const void* d_src, const void* d_base, uint64_t n_elems, uint8_t* d_dst,
+                       fsehip_stream_t stream);
+int fsehip_diff_decode(uint32_t elem_bytes, const uint8_t* d_src, uint64_t n_elems, void* d_dst, const void* d_base,
+                       fsehip_stream_t stream);
+
+/* fsehip_planes_compress with the diff image against d_base in place of the
+ * plane image: the same arguments, alignment rules (d_src and d_base to
+ * elem_bytes, d_scratch to 16, d_out any), capacities
+ * (fsehip_diff_scratch_bytes, fsehip_diff_bound) and statuses, UNSUPPORTED for
+ * elem_bytes outside {1, 2, 4, 8}; nothing allocated for the transform, no
+ * host synchronisation. */
+int fsehip_diff_compress(const fsehip_frame_params* p, uint32_t elem_bytes, const void* d_src, const void* d_base,
+                         uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_cap, uint8_t* d_out, uint64_t out_cap,
+                         uint64_t* d_out_len, int32_t* d_result, fsehip_stream_t stream);
+
+/* fsehip_planes_decompress for a diff frame whose first 48 bytes
+ * fsehip_diff_read_header parsed into `info` and `inner`, against the
+ * info->n_elems elements at d_base: the same arguments, rules and statuses
+ * (d_out 16-byte aligned; d_base itself, the in-place decode, or clear of
+ * it); on BAD_FRAME every block status is BAD_FRAME and no byte of d_out is
+ * touched.  A failed inner block costs the elements with a byte in it; every
+ * other element is exact. */
+int fsehip_diff_decompress(const fsehip_diff_info* info, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                           const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap,
+                           void* d_out, const void* d_base, uint64_t out_cap, int32_t* d_block_status,
+                           int32_t* d_result, fsehip_stream_t stream);
+
+/* The scratch fsehip_diff_decompress_ranges needs for a range list (host
+ * array): fsehip_planes_ranges_scratch_bytes' formula, at elem_bytes 1 too.
+ * 0 for a bad elem_bytes or on overflow. */
+uint64_t fsehip_diff_ranges_scratch_bytes(uint32_t elem_bytes, const fsehip_planes_range* ranges, uint32_t n_ranges);
+
+/* fsehip_planes_decompress_ranges for a diff frame: a range maps to the w
+ * byte ranges of the inner frame a plane range maps to, and its base elements
+ * are d_base[elem_off .. elem_off + n_elems) -- d_base points at the whole
+ * base tensor, info->n_elems elements, whatever the ranges.  The range rules,
+ * statuses and argument checks are those of fsehip_planes_decompress_ranges,
+ * with fsehip_diff_ranges_scratch_bytes for the scratch; and BAD_ARG for a
+ * null d_base with a non-empty range, one not aligned to elem_bytes, or any
+ * overlap of d_out's bytes up to the end of the last destination with the
+ * base. */
+int fsehip_diff_decompress_ranges(const fsehip_diff_info* info, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                                  const uint8_t* d_in, uint64_t in_len, const fsehip_planes_range* ranges,
+                                  uint32_t n_ranges, uint8_t* d_scratch, uint64_t scratch_cap, void* d_out,
+                                  const void* d_base, uint64_t out_cap, int32_t* d_range_status, int32_t* d_result,
+                                  fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
