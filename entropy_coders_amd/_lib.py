@@ -63,6 +63,8 @@ EXPORTS = (
     "fsehip_log2q8", "fsehip_estimate_choose", "fsehip_estimate_block_host", "fsehip_container_kind",
     "fsehip_estimate_image_bytes", "fsehip_image_histogram", "fsehip_estimate_blocks",
     "fsehip_estimate_scratch_bytes", "fsehip_estimate",
+    "fsehip_diff_image_histogram", "fsehip_estimate_base_scratch_bytes", "fsehip_estimate_base",
+    "fsehip_estimate_choose_base",
 )
 
 STATUS = {
@@ -144,7 +146,7 @@ class CheckInfo(C.Structure):
 
 KINDS = ("frame", "planes", "delta")  # FSEHIP_KIND_FRAME / _PLANES / _DELTA
 KIND_SEALED = 3                        # FSEHIP_KIND_SEALED: fsehip_container_kind of an "FSEK" buffer
-KIND_DIFF = 4                          # FSEHIP_KIND_DIFF: of an "FSEB" buffer; no estimate takes it
+KIND_DIFF = 4                          # FSEHIP_KIND_DIFF: of an "FSEB" buffer; fsehip_estimate_base's fifth entry
 EST_NONE = (1 << 64) - 1               # FSEHIP_EST_NONE
 EST_RAW, EST_RLE, EST_FSE = 0, 1, 2    # FSEHIP_EST_*: the frame directory's block types
 
@@ -322,6 +324,11 @@ def load() -> C.CDLL:
     lib.fsehip_estimate_scratch_bytes.argtypes = [u64, u32, u32, u32]
     lib.fsehip_estimate_scratch_bytes.restype = u64
     lib.fsehip_estimate.argtypes = [C.POINTER(FrameParams), u32, u32, P, u64, P, u64, P, P]
+    lib.fsehip_diff_image_histogram.argtypes = [u32, P, P, u64, u32, P, P]
+    lib.fsehip_estimate_base_scratch_bytes.argtypes = [u64, u32, u32, u32]
+    lib.fsehip_estimate_base_scratch_bytes.restype = u64
+    lib.fsehip_estimate_base.argtypes = [C.POINTER(FrameParams), u32, u32, P, P, u64, P, u64, P, P]
+    lib.fsehip_estimate_choose_base.argtypes = [C.POINTER(u64 * 5)]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

@@ -1,8 +1,9 @@
 // fse_capi_estimate.cpp -- the size-estimate calls of the C ABI (fsehip.h
-// section 2g): the cost model, the choice and the sizes in fse_estimate.cpp,
-// kernels in fse_estimate.hip.  fsehip_estimate is, per kind, a zeroed count
-// array, one histogram launch and one estimate launch on the caller's scratch
-// and stream; the frame's counts are fsehip_histogram_blocks'.
+// sections 2g and 2i): the cost model, the choice and the sizes in
+// fse_estimate.cpp, kernels in fse_estimate.hip.  fsehip_estimate and
+// fsehip_estimate_base are, per kind, a zeroed count array, one histogram
+// launch and one estimate launch on the caller's scratch and stream; the
+// frame's counts are fsehip_histogram_blocks'.
 #include "fse_capi_common.h"
 #include "fse_estimate_host.h"
 
@@ -40,15 +41,63 @@ fsehip::EstBlocks est_args(const fsehip_frame_params* p, const uint32_t* counts,
     return E;
 }
 
+// fsehip_estimate_image_bytes, and the diff image, which has the delta image's size
+uint64_t image_bytes(uint32_t kind, uint64_t n_elems, uint32_t w) {
+    return fsehip_estimate_image_bytes(kind == FSEHIP_KIND_DIFF ? FSEHIP_KIND_DELTA : kind, n_elems, w);
+}
+
 // the counts of one kind's image: zeroed and added to, or the frame's own kernel
-int image_counts(uint32_t kind, uint32_t w, const void* d_src, uint64_t n_elems, uint64_t n_image, uint32_t bs,
-                 uint64_t n_blocks, uint32_t* d_counts, fsehip_stream_t stream) {
+int image_counts(uint32_t kind, uint32_t w, const void* d_src, const void* d_base, uint64_t n_elems, uint64_t n_image,
+                 uint32_t bs, uint64_t n_blocks, uint32_t* d_counts, fsehip_stream_t stream) {
     const hipStream_t hs = static_cast<hipStream_t>(stream);
     if (kind == FSEHIP_KIND_FRAME)
         return rc_of(fsehip::launch_histogram(static_cast<const uint8_t*>(d_src), n_image, bs, (uint32_t)n_blocks,
                                               d_counts, nullptr, hs));
     if (hipMemsetAsync(d_counts, 0, 1024ull * n_blocks, hs) != hipSuccess) return FSE_ERR_HIP;
+    if (kind == FSEHIP_KIND_DIFF) return fsehip::launch_diff_histogram(w, d_src, d_base, n_elems, bs, d_counts, stream);
     return fsehip::launch_image_histogram(w, kind == FSEHIP_KIND_DELTA, d_src, n_elems, bs, d_counts, stream);
+}
+
+// fsehip_estimate (n_est = 3: kinds 0..2) and fsehip_estimate_base (n_est = 5:
+// the diff frame too, entry 3 always NONE); the caller has refused the bits
+// its mask does not have
+int estimate_kinds(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t n_est, uint32_t elem_bytes,
+                   const void* d_src, const void* d_base, uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes,
+                   uint64_t* d_est, fsehip_stream_t stream) {
+    if (!p || !d_est || kind_mask == 0u) return FSE_ERR_BAD_ARG;
+    if (!width_ok(elem_bytes)) return FSE_ERR_UNSUPPORTED;
+    uint64_t n_image[5] = {}, n_blocks[5] = {}, fixed[5];
+    uint32_t bs = 0;
+    bool on[5];
+    for (uint32_t k = 0; k < 5; ++k) {
+        on[k] = k < n_est && k != FSEHIP_KIND_SEALED && (kind_mask >> k & 1u) && kind_takes(k, elem_bytes);
+        fixed[k] = FSEHIP_EST_NONE;
+        if (!on[k]) continue;
+        n_image[k] = image_bytes(k, n_elems, elem_bytes);
+        if (n_elems && !n_image[k]) return FSE_ERR_UNSUPPORTED;
+        if (const int rc = frame_rules(p, n_image[k], &bs, &n_blocks[k])) return rc;
+        fixed[k] = (k == FSEHIP_KIND_FRAME ? 32u : 48u) + 4u * n_blocks[k];
+    }
+    const uint64_t need = n_est == 3 ? fsehip_estimate_scratch_bytes(n_elems, elem_bytes, kind_mask, p->block_size)
+                                     : fsehip_estimate_base_scratch_bytes(n_elems, elem_bytes, kind_mask, p->block_size);
+    if (n_elems && (!d_src || (need && !d_scratch))) return FSE_ERR_BAD_ARG;
+    if (!aligned(d_src, elem_bytes) || !aligned(d_scratch, 16) || !aligned(d_est, 8)) return FSE_ERR_BAD_ARG;
+    // the base counts only where the diff frame is asked for and there is something to subtract
+    if (on[FSEHIP_KIND_DIFF] && n_elems && (!d_base || !aligned(d_base, elem_bytes))) return FSE_ERR_BAD_ARG;
+    if (scratch_bytes < need) return FSE_ERR_DST_TOO_SMALL;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    if (const int rc = fsehip::launch_est_init(d_est, fixed, 3, stream)) return rc;
+    if (n_est == 5)
+        if (const int rc = fsehip::launch_est_init(d_est + 3, fixed + 3, 2, stream)) return rc;
+    uint32_t* counts = reinterpret_cast<uint32_t*>(d_scratch);
+    for (uint32_t k = 0; k < n_est; ++k) {
+        if (!on[k] || n_blocks[k] == 0) continue;
+        if (const int rc = image_counts(k, elem_bytes, d_src, d_base, n_elems, n_image[k], bs, n_blocks[k], counts, stream))
+            return rc;
+        const fsehip::EstBlocks E = est_args(p, counts, n_image[k], bs, n_blocks[k], d_est + k);
+        if (const int rc = fsehip::launch_est_blocks(E, stream)) return rc;
+    }
+    return FSE_OK;
 }
 
 }  // namespace
@@ -68,7 +117,7 @@ int fsehip_image_histogram(uint32_t kind, uint32_t elem_bytes, const void* d_src
     const uint64_t n_blocks = (n_image + bs - 1) / bs;
     if ((n_blocks > 1 && (bs & 15u)) || n_blocks > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;
     if (!device_ok()) return FSE_ERR_NO_DEVICE;
-    return image_counts(kind, elem_bytes, d_src, n_elems, n_image, bs, n_blocks, d_counts, stream);
+    return image_counts(kind, elem_bytes, d_src, nullptr, n_elems, n_image, bs, n_blocks, d_counts, stream);
 }
 
 int fsehip_estimate_blocks(const fsehip_frame_params* p, const uint32_t* d_counts, uint64_t n_image_bytes,
@@ -94,35 +143,31 @@ int fsehip_estimate_blocks(const fsehip_frame_params* p, const uint32_t* d_count
 int fsehip_estimate(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t elem_bytes, const void* d_src,
                     uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes, uint64_t* d_est,
                     fsehip_stream_t stream) {
-    if (!p || !d_est || kind_mask == 0u || kind_mask > 7u) return FSE_ERR_BAD_ARG;
+    if (kind_mask > 7u) return FSE_ERR_BAD_ARG;
+    return estimate_kinds(p, kind_mask, 3, elem_bytes, d_src, nullptr, n_elems, d_scratch, scratch_bytes, d_est, stream);
+}
+
+int fsehip_diff_image_histogram(uint32_t elem_bytes, const void* d_src, const void* d_base, uint64_t n_elems,
+                                uint32_t block_size, uint32_t* d_counts, fsehip_stream_t stream) {
     if (!width_ok(elem_bytes)) return FSE_ERR_UNSUPPORTED;
-    uint64_t n_image[3] = {0, 0, 0}, n_blocks[3] = {0, 0, 0}, fixed[3];
-    uint32_t bs = 0;
-    bool on[3];
-    for (uint32_t k = 0; k < 3; ++k) {
-        on[k] = (kind_mask >> k & 1u) && kind_takes(k, elem_bytes);
-        fixed[k] = FSEHIP_EST_NONE;
-        if (!on[k]) continue;
-        n_image[k] = fsehip_estimate_image_bytes(k, n_elems, elem_bytes);
-        if (n_elems && !n_image[k]) return FSE_ERR_UNSUPPORTED;
-        if (const int rc = frame_rules(p, n_image[k], &bs, &n_blocks[k])) return rc;
-        fixed[k] = (k == FSEHIP_KIND_FRAME ? 32u : 48u) + 4u * n_blocks[k];
-    }
-    const uint64_t need = fsehip_estimate_scratch_bytes(n_elems, elem_bytes, kind_mask, p->block_size);
-    if (n_elems && (!d_src || (need && !d_scratch))) return FSE_ERR_BAD_ARG;
-    if (!aligned(d_src, elem_bytes) || !aligned(d_scratch, 16) || !aligned(d_est, 8)) return FSE_ERR_BAD_ARG;
-    if (scratch_bytes < need) return FSE_ERR_DST_TOO_SMALL;
+    if (n_elems == 0) return FSE_OK;
+    const uint64_t n_image = image_bytes(FSEHIP_KIND_DIFF, n_elems, elem_bytes);
+    if (!n_image) return FSE_ERR_UNSUPPORTED;
+    if (!d_src || !d_base || !d_counts || !aligned(d_src, elem_bytes) || !aligned(d_base, elem_bytes) ||
+        !aligned(d_counts, 4))
+        return FSE_ERR_BAD_ARG;
+    const uint32_t bs = block_size ? block_size : kDefaultBlock;
+    const uint64_t n_blocks = (n_image + bs - 1) / bs;
+    if ((n_blocks > 1 && (bs & 15u)) || n_blocks > 0xFFFFFFFFull) return FSE_ERR_BAD_ARG;
     if (!device_ok()) return FSE_ERR_NO_DEVICE;
-    if (const int rc = fsehip::launch_est_init(d_est, fixed, 3, stream)) return rc;
-    uint32_t* counts = reinterpret_cast<uint32_t*>(d_scratch);
-    for (uint32_t k = 0; k < 3; ++k) {
-        if (!on[k] || n_blocks[k] == 0) continue;
-        if (const int rc = image_counts(k, elem_bytes, d_src, n_elems, n_image[k], bs, n_blocks[k], counts, stream))
-            return rc;
-        const fsehip::EstBlocks E = est_args(p, counts, n_image[k], bs, n_blocks[k], d_est + k);
-        if (const int rc = fsehip::launch_est_blocks(E, stream)) return rc;
-    }
-    return FSE_OK;
+    return image_counts(FSEHIP_KIND_DIFF, elem_bytes, d_src, d_base, n_elems, n_image, bs, n_blocks, d_counts, stream);
+}
+
+int fsehip_estimate_base(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t elem_bytes, const void* d_src,
+                         const void* d_base, uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes,
+                         uint64_t* d_est, fsehip_stream_t stream) {
+    if (kind_mask & ~23u) return FSE_ERR_BAD_ARG;  // bits 0, 1, 2 and 4
+    return estimate_kinds(p, kind_mask, 5, elem_bytes, d_src, d_base, n_elems, d_scratch, scratch_bytes, d_est, stream);
 }
 
 }  // extern "C"

@@ -23,28 +23,9 @@ namespace fsehip {
 
 namespace {
 
-// z = zigzag(x - b) for the N / W * 4 elements of the N dwords x and b (N = 4 W:
-// a group of 16; N = W: a quad of 4)
-template <int W, int N>
-__device__ __forceinline__ void diff_zigzag(const uint32_t (&x)[N], const uint32_t (&b)[N], uint32_t (&z)[N]) {
-    using A = typename Acc<W>::type;
-    uint32_t xe[4 * W], be[4 * W], ze[4 * W];
-#pragma unroll
-    for (int j = 0; j < 4 * W; ++j) {
-        xe[j] = j < N ? x[j] : 0u;
-        be[j] = j < N ? b[j] : 0u;
-        ze[j] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 4 * N / W; ++i) {
-        const A d = get<W>(xe, i) - get<W>(be, i);
-        put<W>(ze, i, (A)(d << 1) ^ (A)(0 - ((d >> (8 * W - 1)) & 1u)));
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) z[j] = ze[j];
-}
-
-// the inverse: x = b + unzigzag(z)
+// the inverse of diff_zigzag (fse_planes_dev.hpp): x = b + unzigzag(z) for the
+// N / W * 4 elements of the N dwords z and b (N = 4 W: a group of 16; N = W: a
+// quad of 4)
 template <int W, int N>
 __device__ __forceinline__ void diff_unzigzag(const uint32_t (&z)[N], const uint32_t (&b)[N], uint32_t (&x)[N]) {
     using A = typename Acc<W>::type;

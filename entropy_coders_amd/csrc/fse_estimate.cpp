@@ -1,10 +1,11 @@
-// fse_estimate.cpp -- the size estimate's host side (fsehip.h section 2g):
-// the integer cost model applied to a caller's table, the choice, the sizes
-// and the container's kind from its magic.
+// fse_estimate.cpp -- the size estimate's host side (fsehip.h sections 2g and
+// 2i): the integer cost model applied to a caller's table, the choice among
+// three kinds and, with a base, among four, the sizes and the container's
+// kind from its magic.
 //
 // Plain C++ with no HIP include, as fse_elem.cpp: the same source builds
-// into libfsehip.so and, with g++ alone, into the sanitizer fuzz of
-// tests/native/estimate_fuzz.cpp.  The kernels are fse_estimate.hip, the
+// into libfsehip.so and, with g++ alone, into the sanitizer fuzzes of
+// tests/native/estimate_fuzz.cpp and estimate_diff_fuzz.cpp.  The kernels are fse_estimate.hip, the
 // device calls fse_capi_estimate.cpp.
 #include <string.h>
 
@@ -112,6 +113,29 @@ uint64_t fsehip_estimate_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes, ui
         most = nb > most ? nb : most;
     }
     return most > UINT64_MAX / 1024u ? 0 : most * 1024u;
+}
+
+// ---- section 2i: the diff frame as fourth kind
+
+int fsehip_estimate_choose_base(const uint64_t est[5]) {
+    if (!est) return -1;
+    int best = -1;
+    for (int k = 0; k < 5; ++k)
+        if (k != (int)FSEHIP_KIND_SEALED && est[k] != FSEHIP_EST_NONE && (best < 0 || est[k] < est[best])) best = k;
+    return best;
+}
+
+uint64_t fsehip_estimate_base_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes, uint32_t kind_mask,
+                                            uint32_t block_size) {
+    if (kind_mask == 0u || (kind_mask & ~23u) || !width_ok(elem_bytes)) return 0;
+    uint64_t most = kind_mask & 7u ? fsehip_estimate_scratch_bytes(n_elems, elem_bytes, kind_mask & 7u, block_size) : 0;
+    if (kind_mask & 16u) {
+        // the diff image has the delta image's size, the largest: where another overflows, it does
+        const uint64_t diff = fsehip_estimate_scratch_bytes(n_elems, elem_bytes, 1u << FSEHIP_KIND_DELTA, block_size);
+        if (n_elems && !diff) return 0;
+        most = diff > most ? diff : most;
+    }
+    return most;
 }
 
 }  // extern "C"

@@ -1,9 +1,11 @@
-// fse_estimate.hip -- the kernels of the size estimate (fsehip.h section 2g),
-// gfx950.
+// fse_estimate.hip -- the kernels of the size estimate (fsehip.h sections 2g
+// and 2i), gfx950.
 //
 //   image_histogram_kernel<W, DELTA>  raw elements -> the 256-bin counts of
 //                                     every block of the plane or delta image,
 //                                     without writing the image
+//   diff_histogram_kernel<W>          raw elements and the base's -> the same
+//                                     of the diff image
 //   estimate_blocks_kernel            a block's counts -> the estimated type,
 //                                     record bytes, payload bits and table log
 //   est_init_kernel                   the containers' fixed bytes
@@ -183,6 +185,110 @@ __global__ __launch_bounds__(PL_T) __attribute__((amdgpu_waves_per_eu(4))) void 
     }
 }
 
+// image_histogram_kernel's structure over two sources: the tiles, the
+// sub-histograms, the flush and the small-block path are the same, the text is
+// its own so that the seven instances above keep their registers.  A lane
+// issues the 16-byte loads of its 16 elements and of the base's same 16 before
+// it uses either, then takes the diff frame's own zigzag (diff_zigzag of
+// fse_planes_dev.hpp, as diff_split_kernel) in place over the source's
+// registers.  An element depends on its own base element only: no restart, and
+// src and base may overlap in any way (neither is written).  Diff images are
+// mostly zero high planes: count16<true> adds such a wave's 1,024 bytes once.
+template <int W>
+__global__ __launch_bounds__(PL_T) __attribute__((amdgpu_waves_per_eu(4))) void diff_histogram_kernel(
+    const uint8_t* src, const uint8_t* base, uint64_t n_elems, uint32_t bs, uint32_t tiles_per_wg,
+    uint32_t* __restrict__ counts) {
+    constexpr uint32_t C = ih_copies<W>();
+    __shared__ __attribute__((aligned(16))) uint32_t hist[W * 256u * C];  // [plane][bin][copy]
+    const uint64_t groups = (n_elems + 15u) >> 4, stride = groups << 4;
+    const uint64_t tiles = (groups + PL_T - 1u) / PL_T;
+    const uint64_t t0 = (uint64_t)blockIdx.x * tiles_per_wg;
+    if (t0 >= tiles) return;
+    const uint64_t t1 = t0 + tiles_per_wg < tiles ? t0 + tiles_per_wg : tiles;
+    const bool direct = bs < IH_TILE;
+    const uint32_t tid = threadIdx.x;
+    uint32_t* const mine = hist + (tid & (C - 1u));
+
+    uint64_t cur[W], bound[W];
+    if (!direct) {
+        for (uint32_t i = tid; i < W * 256u * C; i += PL_T) hist[i] = 0;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            cur[k] = (k * stride + t0 * IH_TILE) / bs;
+            bound[k] = (cur[k] + 1u) * bs;
+        }
+        __syncthreads();
+    }
+    auto flush = [&](int k) {
+        __syncthreads();
+        uint32_t* h = hist + (k * 256u + tid) * C;
+        uint32_t sum = 0;
+#pragma unroll
+        for (uint32_t c = 0; c < C; c += 4) {
+            const uint4 v = *reinterpret_cast<const uint4*>(h + c);
+            sum += v.x + v.y + v.z + v.w;
+            *reinterpret_cast<uint4*>(h + c) = make_uint4(0, 0, 0, 0);
+        }
+        if (sum) atomicAdd(counts + cur[k] * 256u + tid, sum);
+        __syncthreads();
+    };
+
+    for (uint64_t tile = t0; tile < t1; ++tile) {
+        const uint64_t g = tile * PL_T + tid;
+        const bool active = g < groups;
+        uint32_t p[W][4];
+        if (active) {
+            const bool whole = (g << 4) + 16u <= n_elems;
+            const uint32_t rem = whole ? 16u * W : (uint32_t)(n_elems - (g << 4)) * W;
+            uint32_t x[4 * W], b[4 * W];
+            load_group<W>(src + g * (16u * W), whole, rem, x);
+            load_group<W>(base + g * (16u * W), whole, rem, b);
+            diff_zigzag<W, 4 * W>(x, b, x);
+            if (!whole) zero_pad<W>(x, rem);
+            if constexpr (W == 1) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) p[0][j] = x[j];
+            } else {
+                deinterleave<W>(x, p);
+            }
+        }
+        if (direct) {
+            if (active) {
+#pragma unroll
+                for (int k = 0; k < W; ++k) {
+                    uint32_t* c = counts + (k * stride + (g << 4)) / bs * 256u;
+                    count16<false>(p[k], [&](uint32_t byte, uint32_t inc) { atomicAdd(c + byte, inc); });
+                }
+            }
+            continue;
+        }
+        const uint64_t tile_off = tile * IH_TILE;
+        const uint64_t tile_len = stride - tile_off < IH_TILE ? stride - tile_off : IH_TILE;
+#pragma unroll
+        for (int k = 0; k < W; ++k) {
+            const uint64_t at = k * stride + tile_off;  // the tile's first byte of plane k in the image
+            auto add = [&](uint32_t byte, uint32_t inc) { atomicAdd(mine + (k * 256u + byte) * C, inc); };
+            if (at >= bound[k]) {
+                flush(k);
+                cur[k] += 1u;
+                bound[k] += bs;
+            }
+            const bool first = at + ((uint64_t)tid << 4) < bound[k];
+            if (active && first) count16<true>(p[k], add);
+            if (at + tile_len > bound[k]) {
+                flush(k);
+                cur[k] += 1u;
+                bound[k] += bs;
+                if (active && !first) count16<true>(p[k], add);
+            }
+        }
+    }
+    if (!direct) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) flush(k);
+    }
+}
+
 // One wave per block.  What the histogram alone decides of the encoder's
 // status decides the type: ALL_ZERO_SYMBOL0 is RLE, any other refusal RAW.
 __global__ __launch_bounds__(64) void estimate_blocks_kernel(EstBlocks E) {
@@ -281,7 +387,29 @@ void ih_launch(const uint8_t* src, uint64_t n_elems, uint32_t bs, uint32_t* coun
                        counts);
 }
 
+template <int W>
+void dh_launch(const uint8_t* src, const uint8_t* base, uint64_t n_elems, uint32_t bs, uint32_t* counts,
+               hipStream_t hs) {
+    const uint64_t tiles = (n_elems + IH_TILE - 1u) / IH_TILE;
+    const uint32_t grid = (uint32_t)(tiles < PL_MAX_WGS ? tiles : PL_MAX_WGS);
+    const uint32_t per = (uint32_t)((tiles + grid - 1u) / grid);
+    hipLaunchKernelGGL(diff_histogram_kernel<W>, dim3(grid), dim3(PL_T), 0, hs, src, base, n_elems, bs, per, counts);
+}
+
 }  // namespace
+
+int launch_diff_histogram(uint32_t w, const void* src, const void* base, uint64_t n_elems, uint32_t block_size,
+                          uint32_t* counts, void* stream) {
+    if (n_elems == 0) return FSE_OK;
+    const hipStream_t hs = static_cast<hipStream_t>(stream);
+    const uint8_t* s = static_cast<const uint8_t*>(src);
+    const uint8_t* b = static_cast<const uint8_t*>(base);
+    if (w == 1) dh_launch<1>(s, b, n_elems, block_size, counts, hs);
+    else if (w == 2) dh_launch<2>(s, b, n_elems, block_size, counts, hs);
+    else if (w == 4) dh_launch<4>(s, b, n_elems, block_size, counts, hs);
+    else dh_launch<8>(s, b, n_elems, block_size, counts, hs);
+    return done();
+}
 
 int launch_image_histogram(uint32_t w, bool delta, const void* src, uint64_t n_elems, uint32_t block_size,
                            uint32_t* counts, void* stream) {

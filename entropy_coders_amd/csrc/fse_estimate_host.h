@@ -1,5 +1,5 @@
 // fse_estimate_host.h -- what the size estimate's translation units share
-// (fsehip.h section 2g): the integer cost model of fse_estimate.cpp, written
+// (fsehip.h sections 2g and 2i): the integer cost model of fse_estimate.cpp, written
 // once for the host and the device, and the launchers of fse_estimate.hip,
 // called by fse_capi_estimate.cpp.  Plain C++ with no HIP include (a stream
 // travels as void*), as fse_elem_host.h.  Not part of the public ABI.
@@ -80,5 +80,8 @@ int launch_est_blocks(const EstBlocks& E, void* stream);
 // image's blocks, added into `counts`, which the caller has zeroed
 int launch_image_histogram(uint32_t w, bool delta, const void* src, uint64_t n_elems, uint32_t block_size,
                            uint32_t* counts, void* stream);
+// the same of the diff image (w 1, 2, 4, 8) of src against base, which may overlap
+int launch_diff_histogram(uint32_t w, const void* src, const void* base, uint64_t n_elems, uint32_t block_size,
+                          uint32_t* counts, void* stream);
 
 }  // namespace fsehip

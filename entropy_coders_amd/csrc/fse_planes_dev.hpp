@@ -2,7 +2,7 @@
 // fsehip.h section 2d), the delta transforms (fse_delta.hip, section 2e) and
 // the image histogram (fse_estimate.hip, section 2g) share: the launch shape,
 // the under-aligned access types, the byte transposes on v_perm_b32, and the
-// group load and zigzag delta of the element side.  Element i of a 16-element
+// group load and the zigzag delta and diff of the element side.  Element i of a 16-element
 // group is the dwords [i * W / 4, (i + 1) * W / 4) of the lane's 4 W.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -190,6 +190,28 @@ __device__ __forceinline__ void delta_zigzag(const uint8_t* __restrict__ s, bool
         prev = x;
         put<W>(z, i, (A)(d << 1) ^ (A)(0 - ((d >> (8 * W - 1)) & 1u)));
     }
+}
+
+// The diff frame's transform (fse_diff.hip) and its histogram
+// (fse_estimate.hip): z = zigzag(x - b) for the N / W * 4 elements of the N
+// dwords x and b (N = 4 W: a group of 16; N = W: a quad of 4).  z may be x.
+template <int W, int N>
+__device__ __forceinline__ void diff_zigzag(const uint32_t (&x)[N], const uint32_t (&b)[N], uint32_t (&z)[N]) {
+    using A = typename Acc<W>::type;
+    uint32_t xe[4 * W], be[4 * W], ze[4 * W];
+#pragma unroll
+    for (int j = 0; j < 4 * W; ++j) {
+        xe[j] = j < N ? x[j] : 0u;
+        be[j] = j < N ? b[j] : 0u;
+        ze[j] = 0;
+    }
+#pragma unroll
+    for (int i = 0; i < 4 * N / W; ++i) {
+        const A d = get<W>(xe, i) - get<W>(be, i);
+        put<W>(ze, i, (A)(d << 1) ^ (A)(0 - ((d >> (8 * W - 1)) & 1u)));
+    }
+#pragma unroll
+    for (int j = 0; j < N; ++j) z[j] = ze[j];
 }
 
 // workgroups for `items` lanes' worth of work, capped

@@ -44,6 +44,9 @@ _ELEM = {"planes": _ElemKind("fsehip_planes_", "split", "merge", (2, 4, 8), Plan
          "delta": _ElemKind("fsehip_delta_", "encode", "decode", (1, 2, 4, 8), DeltaInfo, "delta"),
          "diff": _ElemKind("fsehip_diff_", "encode", "decode", (1, 2, 4, 8), DiffInfo, "diff", based=True)}
 
+# fsehip_estimate_base's five entries by FSEHIP_KIND_*: entry 3 (sealed) is no choice of container
+_BASE_KINDS = KINDS + (None, "diff")
+
 _tls = threading.local()
 
 
@@ -1302,8 +1305,17 @@ class BlockCodec:
             raise ValueError(f"kind {kind!r}: 'frame', 'planes', 'delta' or 'diff'")
         return self._elem_width(kind, x)
 
+    @staticmethod
+    def _sealed_candidates(x, base=None) -> tuple:
+        """What kind='auto' chooses among: a sealed frame takes 1-byte tensors
+        only, a plane frame wider ones only, a diff frame needs the base."""
+        return ("frame" if x.element_size() == 1 else "planes", "delta") + (("diff",) if base is not None else ())
+
     def sealed_bound(self, x, kind: str = "frame", check_block: int = 65536) -> int:
-        """A capacity no sealed buffer of `x` exceeds: the record, then the container's bound."""
+        """A capacity no sealed buffer of `x` exceeds: the record, then the
+        container's bound; for kind 'auto' the largest of the candidates'."""
+        if kind == "auto":
+            return max(self.sealed_bound(x, k, check_block) for k in self._sealed_candidates(x) + ("diff",))
         w = self._sealed_kind(x, kind)
         inner = self.frame_bound(x.numel()) if kind == "frame" else self._elem_bound(kind, x.numel(), w)
         return self.check_bytes(self._content_bytes(x), check_block) + inner
@@ -1334,8 +1346,17 @@ class BlockCodec:
         """Compress a contiguous device tensor into one sealed buffer (a check
         record, then a frame, plane frame, delta frame or -- kind 'diff',
         against `base` -- diff frame): a uint8 device tensor of its exact
-        length.  One synchronisation, to read the length."""
+        length.  One synchronisation, to read the length.  kind 'auto'
+        estimates first (one more synchronisation) and seals the kind
+        `estimate_choose` picks among the frame (1-byte tensors), the plane
+        frame (wider ones), the delta frame and, with `base`, the diff frame:
+        the buffer is compress_sealed's of that kind, which sealed_info names."""
         t = self.torch
+        if kind == "auto":
+            if base is not None:
+                self._elem_base("diff", base, x.numel(), x.dtype)
+            kind = estimate_choose(self.estimate(x, self._sealed_candidates(x, base), base))
+            base = base if kind == "diff" else None
         w = self._sealed_kind(x, kind)
         scratch = None
         if kind != "frame":
@@ -1495,15 +1516,21 @@ class BlockCodec:
         return views[0]
 
     # ------------------------------------------------------------ the size estimate
-    # fsehip.h section 2g: the length each container would have, from the
-    # block histograms of its image and the encoder's own normalisation, and
-    # the automatic choice among compress_frame / compress_planes /
-    # compress_delta.  Kinds are "frame", "planes", "delta" (or 0, 1, 2).
+    # fsehip.h sections 2g and 2i: the length each container would have, from
+    # the block histograms of its image and the encoder's own normalisation,
+    # and the automatic choice among compress_frame / compress_planes /
+    # compress_delta and, for a caller who passes the tensor's base,
+    # compress_diff.  Kinds are "frame", "planes", "delta" (or 0, 1, 2) and,
+    # with base=, "diff" (or 4).
     @staticmethod
-    def _kind(kind) -> int:
+    def _kind(kind, base=None) -> int:
         k = KINDS.index(kind) if isinstance(kind, str) and kind in KINDS else kind
+        if base is not None and kind in ("diff", KIND_DIFF):
+            return KIND_DIFF
         if k not in (0, 1, 2):
-            raise ValueError(f"kind {kind!r}: one of {KINDS}")
+            if kind in ("diff", KIND_DIFF):
+                raise ValueError("kind 'diff' estimates against a base: pass base=")
+            raise ValueError(f"kind {kind!r}: one of {KINDS}" + (" or 'diff'" if base is not None else ""))
         return k
 
     @staticmethod
@@ -1515,30 +1542,50 @@ class BlockCodec:
             raise ValueError("the estimate needs a contiguous tensor")
         return w
 
-    def _kind_mask(self, kinds) -> int:
-        """Bit k for every kind asked for (None: all three); a kind that does
-        not take the width stays in the mask and is estimated as EST_NONE."""
+    def _kind_mask(self, kinds, base=None) -> int:
+        """Bit k for every kind asked for (None: all three, and with a base
+        the diff frame); a kind that does not take the width stays in the mask
+        and is estimated as EST_NONE."""
         mask = 0
-        for kind in (KINDS if kinds is None else kinds):
-            mask |= 1 << self._kind(kind)
+        for kind in (KINDS + (("diff",) if base is not None else ()) if kinds is None else kinds):
+            mask |= 1 << self._kind(kind, base)
         if mask == 0:
             raise ValueError("no kind asked for")
         return mask
+
+    @staticmethod
+    def _estimate_base(x, base):
+        """The base of an estimate after its checks (ValueError): a contiguous
+        device tensor of x's element width and element count."""
+        if not hasattr(base, "data_ptr") or not base.is_cuda:
+            raise ValueError("base must be a device tensor")
+        if not base.is_contiguous():
+            raise ValueError("base must be contiguous")
+        if base.element_size() != x.element_size() or base.numel() != x.numel():
+            raise ValueError(f"base has {base.numel()} elements of {base.element_size()} bytes, the tensor "
+                             f"{x.numel()} of {x.element_size()}")
+        return C.c_void_p(base.data_ptr())
 
     def _frame_params(self, chunk_blocks: int = 0) -> FrameParams:
         return FrameParams(self.block_size, self.table_log, self.ckpt_interval, self.max_table_log, self.nstates,
                            chunk_blocks)
 
-    def image_histogram(self, x, kind):
+    def image_histogram(self, x, kind, base=None):
         """`fsehip_image_histogram`: the 256-bin byte counts of every block
         (the codec's block size) of the image the container of `kind` codes
         for the contiguous device tensor x -- its raw bytes, its plane image
-        or its delta image, the images themselves never written.  A uint32
-        device tensor [n_blocks, 256]; no synchronisation."""
+        or its delta image, or (`fsehip_diff_image_histogram`, kind "diff")
+        its diff image against `base` -- the images themselves never written.
+        A uint32 device tensor [n_blocks, 256]; no synchronisation."""
         t = self.torch
-        w, k = self._estimate_elem_bytes(x), self._kind(kind)
-        n_image = int(self.lib.fsehip_estimate_image_bytes(k, x.numel(), w))
+        w, k = self._estimate_elem_bytes(x), self._kind(kind, base)
+        n_image = int(self.lib.fsehip_estimate_image_bytes(2 if k == KIND_DIFF else k, x.numel(), w))
         counts = t.zeros((self.n_blocks(n_image), 256), dtype=t.int32, device=self.device).view(t.uint32)
+        if k == KIND_DIFF:
+            check(self.lib.fsehip_diff_image_histogram(
+                w, C.c_void_p(x.data_ptr()), self._estimate_base(x, base), x.numel(), self.block_size,
+                C.c_void_p(counts.data_ptr()), self._stream()), "fsehip_diff_image_histogram")
+            return counts
         check(self.lib.fsehip_image_histogram(k, w, C.c_void_p(x.data_ptr()), x.numel(), self.block_size,
                                               C.c_void_p(counts.data_ptr()), self._stream()), "fsehip_image_histogram")
         return counts
@@ -1564,50 +1611,73 @@ class BlockCodec:
             C.c_void_p(out["total"].data_ptr()), self._stream()), "fsehip_estimate_blocks")
         return out
 
-    def estimate_scratch_bytes(self, x, kinds=None) -> int:
-        """`fsehip_estimate_scratch_bytes` for x and the kinds asked for."""
+    def estimate_scratch_bytes(self, x, kinds=None, base=None) -> int:
+        """`fsehip_estimate_scratch_bytes` for x and the kinds asked for; with
+        a base `fsehip_estimate_base_scratch_bytes`."""
         w = self._estimate_elem_bytes(x)
+        if base is not None:
+            self._estimate_base(x, base)
+            return int(self.lib.fsehip_estimate_base_scratch_bytes(x.numel(), w, self._kind_mask(kinds, base),
+                                                                   self.block_size))
         return int(self.lib.fsehip_estimate_scratch_bytes(x.numel(), w, self._kind_mask(kinds), self.block_size))
 
-    def estimate_into(self, x, scratch, est, kinds=None) -> None:
+    def estimate_into(self, x, scratch, est, kinds=None, base=None) -> None:
         """`fsehip_estimate`, no synchronisation: `scratch` a uint8 device
         tensor of >= estimate_scratch_bytes (16-byte aligned), `est` three
         int64 on the device, est[k] = the estimated length of kind k or -1
         (FSEHIP_EST_NONE read as int64) for a kind not asked for or not
-        taking the element width."""
+        taking the element width.  With a base `fsehip_estimate_base`: `est`
+        FIVE int64, est[3] always -1, est[4] the diff frame's against `base`."""
         w = self._estimate_elem_bytes(x)
         p = self._frame_params()
+        if base is not None:
+            if est.numel() < 5:
+                raise ValueError("with a base the estimate writes five int64")
+            check(self.lib.fsehip_estimate_base(
+                C.byref(p), self._kind_mask(kinds, base), w, C.c_void_p(x.data_ptr()), self._estimate_base(x, base),
+                x.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(est.data_ptr()),
+                self._stream()), "fsehip_estimate_base")
+            return
         check(self.lib.fsehip_estimate(
             C.byref(p), self._kind_mask(kinds), w, C.c_void_p(x.data_ptr()), x.numel(),
             C.c_void_p(scratch.data_ptr()), scratch.numel(), C.c_void_p(est.data_ptr()), self._stream()),
             "fsehip_estimate")
 
-    def estimate(self, x, kinds=None) -> dict:
+    def estimate(self, x, kinds=None, base=None) -> dict:
         """The estimated container length of a contiguous device tensor for
         each kind of `kinds` (None: all that take its element width): a dict
         kind name -> bytes, under the codec's block size, table log,
         checkpoint interval and nstates.  One synchronisation: the 24-byte
-        copy of the three estimates to the host."""
+        copy of the three estimates to the host.  With `base`, a contiguous
+        device tensor of x's element width and count (ValueError otherwise),
+        "diff" -- the diff frame of x against it -- is a fourth kind and among
+        the default ones; the copy is 40 bytes."""
         t = self.torch
-        scratch = t.empty(max(self.estimate_scratch_bytes(x, kinds), 16), dtype=t.uint8, device=self.device)
-        est = t.zeros(3, dtype=t.int64, device=self.device)
-        self.estimate_into(x, scratch, est, kinds)
+        scratch = t.empty(max(self.estimate_scratch_bytes(x, kinds, base), 16), dtype=t.uint8, device=self.device)
+        est = t.zeros(3 if base is None else 5, dtype=t.int64, device=self.device)
+        self.estimate_into(x, scratch, est, kinds, base)
         host = est.cpu().numpy().view(np.uint64)
-        return {KINDS[k]: int(host[k]) for k in range(3) if int(host[k]) != EST_NONE}
+        names = KINDS if base is None else _BASE_KINDS
+        return {name: int(host[k]) for k, name in enumerate(names) if name and int(host[k]) != EST_NONE}
 
-    def compress_auto(self, x, kinds=None, chunk_blocks: int = 0):
+    def compress_auto(self, x, kinds=None, chunk_blocks: int = 0, base=None):
         """Estimate, choose (`estimate_choose`: the smallest, ties to frame,
-        then planes, then delta) and compress: (buf, kind name), buf exactly
-        what compress_frame / compress_planes / compress_delta returns for
-        that kind.  The frame codes the tensor's bytes.  Two synchronisations:
-        the estimate's and the length's."""
-        est = self.estimate(x, kinds)
+        then planes, then delta, then diff) and compress: (buf, kind name),
+        buf exactly what compress_frame / compress_planes / compress_delta
+        returns for that kind -- or, with `base` (a contiguous device tensor
+        of x's dtype and element count), compress_diff(x, base), which wins
+        only when strictly smaller: it needs the base to decode.  The frame
+        codes the tensor's bytes.  Two synchronisations: the estimate's and
+        the length's."""
+        if base is not None:
+            self._elem_base("diff", base, x.numel(), x.dtype)
+        est = self.estimate(x, kinds, base)
         kind = estimate_choose(est)
         if kind == "frame":
             t = self.torch  # (an empty tensor has no stride to view through)
             raw = x.reshape(-1).view(t.uint8) if x.numel() else t.empty(0, dtype=t.uint8, device=self.device)
             return self.compress_frame(raw, chunk_blocks), kind
-        return self._elem_compress(kind, x, chunk_blocks), kind
+        return self._elem_compress(kind, x, chunk_blocks, base if kind == "diff" else None), kind
 
     def decompress_auto(self, buf, dtype, chunk_blocks: int = 0, base=None):
         """Decode a frame, plane frame, delta frame or diff frame (a uint8
@@ -1784,7 +1854,17 @@ def estimate_choose(est):
     """`fsehip_estimate_choose`: the kind name of the smallest estimate of a
     dict kind name -> bytes (BlockCodec.estimate's) or a 3-sequence indexed by
     kind with EST_NONE for a missing one; ties go to frame, then planes, then
-    delta.  ValueError when there is nothing to choose from."""
+    delta.  A dict with "diff" or a 5-sequence (entry 3 takes no part) goes to
+    `fsehip_estimate_choose_base`: the diff frame is last in a tie.
+    ValueError when there is nothing to choose from."""
+    if isinstance(est, dict) and "diff" in est:
+        est = [est.get(name, EST_NONE) if name else EST_NONE for name in _BASE_KINDS]
+    if not isinstance(est, dict) and len(est) == 5:
+        arr = (C.c_uint64 * 5)(*[int(v) for v in est])
+        k = load().fsehip_estimate_choose_base(C.byref(arr))
+        if k < 0:
+            raise ValueError("no estimate to choose from")
+        return _BASE_KINDS[k]
     if isinstance(est, dict):
         est = [est.get(name, EST_NONE) for name in KINDS]
     arr = (C.c_uint64 * 3)(*[int(v) for v in est])
@@ -1811,11 +1891,12 @@ def container_kind(buf) -> str:
 
 
 def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
-                  nstates: int = 2, device=None):
+                  nstates: int = 2, device=None, base=None):
     """Compress a numpy array of item size 1, 2, 4 or 8 into whichever of the
-    frame, the plane frame and the delta frame the estimate finds smallest
-    (BlockCodec.compress_auto) on the GPU; copies through torch.  Returns
-    (bytes, kind name)."""
+    frame, the plane frame and the delta frame -- and, with `base`, an array
+    of its dtype and size, the diff frame against it -- the estimate finds
+    smallest (BlockCodec.compress_auto) on the GPU; copies through torch.
+    Returns (bytes, kind name)."""
     import torch
 
     a = np.ascontiguousarray(data)
@@ -1824,7 +1905,8 @@ def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0,
     codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
                        nstates=nstates)
     src = torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device)
-    buf, kind = codec.compress_auto(src, kinds)
+    dbase = None if base is None else torch.from_numpy(_host_base(a, base).copy()).to(codec.device)
+    buf, kind = codec.compress_auto(src, kinds, base=dbase)
     return buf.cpu().numpy().tobytes(), kind
 
 
@@ -1860,7 +1942,10 @@ def sealed_compress(data, kind: str = "frame", check_block: int = 65536, block_s
     """Compress a host buffer into one sealed buffer (fsehip.h section 2f) on
     the GPU: bytes or any numpy array for kind 'frame', a numpy array of item
     size 2, 4 or 8 for 'planes' and of 1, 2, 4 or 8 for 'delta' and for
-    'diff', which codes it against `base`, an array of its dtype and size."""
+    'diff', which codes it against `base`, an array of its dtype and size.
+    kind 'auto' (a numpy array of item size 1, 2, 4 or 8, or bytes) seals the
+    kind the estimate finds smallest, the diff frame among them when `base`
+    is given (BlockCodec.compress_sealed)."""
     import torch
 
     codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
@@ -1868,10 +1953,10 @@ def sealed_compress(data, kind: str = "frame", check_block: int = 65536, block_s
     if kind == "frame":
         a = _buf(data) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data).reshape(-1).view(np.uint8)
     else:
-        a = np.ascontiguousarray(data)
+        a = np.ascontiguousarray(data) if isinstance(data, np.ndarray) or kind != "auto" else _buf(data)
         if a.dtype.itemsize not in _INT_VIEW:
             raise ValueError(f"item size {a.dtype.itemsize}: 1, 2, 4 or 8 bytes")
-        if kind == "diff":
+        if kind == "diff" or (kind == "auto" and base is not None):
             base = torch.from_numpy(_host_base(a, base).copy()).to(codec.device)
         a = a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize])
     src = torch.from_numpy(a.copy()).to(codec.device)

@@ -1244,7 +1244,7 @@ int fsehip_check_verify_ranges(const fsehip_check_info* info, const uint8_t* d_r
 #define FSEHIP_KIND_PLANES 1u /* section 2d, magic "FSEP" */
 #define FSEHIP_KIND_DELTA 2u  /* section 2e, magic "FSED" */
 #define FSEHIP_KIND_SEALED 3u /* section 2f, magic "FSEK": fsehip_container_kind only */
-#define FSEHIP_KIND_DIFF 4u   /* section 2h, magic "FSEB": fsehip_container_kind only; no estimate */
+#define FSEHIP_KIND_DIFF 4u   /* section 2h, magic "FSEB": fsehip_container_kind and the calls of section 2i */
 #define FSEHIP_EST_NONE UINT64_MAX /* an estimate that was not asked for or does not exist */
 #define FSEHIP_EST_RAW 0u /* block types, the frame directory's */
 #define FSEHIP_EST_RLE 1u
@@ -1272,7 +1272,8 @@ typedef struct {
  *  fsehip_container_kind: the FSEHIP_KIND_* value of a buffer's magic (host
  *    pointer, len = bytes available; a sealed buffer reports
  *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's;
- *    a diff frame of section 2h FSEHIP_KIND_DIFF, which no estimate call takes),
+ *    a diff frame of section 2h FSEHIP_KIND_DIFF, which the estimate calls of
+ *    section 2i take and those of this section refuse),
  *    FSE_ERR_BAD_FRAME for len < 4 or any other magic, BAD_ARG for a null buf
  *    with len > 0.  Only the magic is read; the headers have their readers. */
 uint32_t fsehip_log2q8(uint32_t c);
@@ -1492,6 +1493,64 @@ int fsehip_diff_decompress_ranges(const fsehip_diff_info* info, const fsehip_fra
                                   uint32_t n_ranges, uint8_t* d_scratch, uint64_t scratch_cap, void* d_out,
                                   const void* d_base, uint64_t out_cap, int32_t* d_range_status, int32_t* d_result,
                                   fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * (2i) Size estimates with a base: the diff frame as fourth kind
+ *
+ * A caller who holds the tensor's previous version can have a diff frame
+ * (section 2h); whether it pays depends on how close the two are (DESIGN.md
+ * section 5 "Estimate": a fifth of the plane frame after a small step, 5 %
+ * more than it for unrelated tensors).  Once the caller hands the base over,
+ * that is again something a histogram finds: the diff image's block counts,
+ * taken from the two sources without writing the image, through the block
+ * rule of section 2g unchanged.  A diff frame: 16 + the frame estimate of its
+ * image.  No format changes, and the calls of section 2g stay as they are:
+ * kinds above 2 are theirs to refuse.
+ * ------------------------------------------------------------------------ */
+
+/* fsehip_image_histogram for the diff image (section 2h) of the n_elems
+ * elements of elem_bytes (1, 2, 4, 8) at d_src against those at d_base: the
+ * counts of its ceil(elem_bytes * roundup(n_elems, 16) / block_size) blocks,
+ * zeroed by the call and then added to.  Both sources are read once, aligned
+ * to elem_bytes each on its own, up to roundup(n_elems * elem_bytes, 4) at
+ * most; they may overlap in any way or be one pointer (every count then in
+ * bin 0).  Nothing but d_counts is written.  Asynchronous on `stream`, no
+ * host synchronisation, no workspace.  Before any device use: UNSUPPORTED
+ * (elem_bytes outside {1, 2, 4, 8}, a size overflowing), BAD_ARG (a null or
+ * misaligned d_src, d_base or d_counts with n_elems > 0, more than one block
+ * of a size that is no multiple of 16, more than 2^32 - 1 blocks), NO_DEVICE.
+ * n_elems == 0 returns FSE_OK and does nothing. */
+int fsehip_diff_image_histogram(uint32_t elem_bytes, const void* d_src, const void* d_base, uint64_t n_elems,
+                                uint32_t block_size, uint32_t* d_counts, fsehip_stream_t stream);
+
+/* fsehip_estimate_scratch_bytes for a kind_mask of bits 0, 1, 2 (as there)
+ * and 4 (FSEHIP_KIND_DIFF, whose image has the delta image's size).  0 for a
+ * kind_mask of 0, with bit 3 or any bit above 4, and as there. */
+uint64_t fsehip_estimate_base_scratch_bytes(uint64_t n_elems, uint32_t elem_bytes, uint32_t kind_mask,
+                                            uint32_t block_size);
+
+/* fsehip_estimate with the diff frame against d_base as a further kind:
+ * kind_mask has bits 0, 1, 2 and 4, and d_est is FIVE u64 on the device,
+ * indexed by FSEHIP_KIND_*.  d_est[3] (a sealed buffer is no choice of
+ * container) is always FSEHIP_EST_NONE; d_est[4] = 16 + 32 + 4 * n_blocks +
+ * the sum of rec over the diff image's blocks, 48 for n_elems = 0, or
+ * FSEHIP_EST_NONE when bit 4 is clear.  With bit 4 clear d_est[0..2] are what
+ * fsehip_estimate gives for the same mask, and d_base is ignored; with bit 4
+ * set and n_elems > 0 a null d_base, or one not aligned to elem_bytes, is
+ * BAD_ARG.  A kind_mask of 0, with bit 3 or with any bit above 4 is BAD_ARG;
+ * d_scratch is fsehip_estimate_base_scratch_bytes; every other rule, status
+ * and promise (one scratch, the kinds one after the other, asynchronous, no
+ * workspace, no host synchronisation) is fsehip_estimate's. */
+int fsehip_estimate_base(const fsehip_frame_params* p, uint32_t kind_mask, uint32_t elem_bytes, const void* d_src,
+                         const void* d_base, uint64_t n_elems, uint8_t* d_scratch, uint64_t scratch_bytes,
+                         uint64_t* d_est, fsehip_stream_t stream);
+
+/* Host function, no device: the kind of the smallest entry of est[5] (indexed
+ * by FSEHIP_KIND_*).  Ties go to the frame, then the plane frame, then the
+ * delta frame, then the diff frame: a container that needs its base to decode
+ * wins only when strictly smaller.  est[3] and entries of FSEHIP_EST_NONE do
+ * not take part; -1 when nothing is left or est is null. */
+int fsehip_estimate_choose_base(const uint64_t est[5]);
 
 /* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
