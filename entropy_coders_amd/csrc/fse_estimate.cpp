@@ -86,6 +86,7 @@ int fsehip_container_kind(const uint8_t* buf, size_t len) {
         case 'D': return (int)FSEHIP_KIND_DELTA;
         case 'K': return (int)FSEHIP_KIND_SEALED;
         case 'B': return (int)FSEHIP_KIND_DIFF;
+        case 'M': return (int)FSEHIP_KIND_PACK;
         default: return FSE_ERR_BAD_FRAME;
     }
 }

@@ -11,10 +11,10 @@ import threading
 
 import numpy as np
 
-from ._lib import (EST_NONE, KIND_DIFF, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState, BitStackWriterState,
-                   BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, DiffInfo, EncodeTable, FrameInfo,
-                   FrameParams, FrameRange, FseError, Histogram, NormHistogram, Params, PlanesInfo, PlanesRange, check,
-                   load)
+from ._lib import (EST_NONE, KIND_DIFF, KIND_PACK, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState,
+                   BitStackWriterState, BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, DiffInfo, EncodeTable,
+                   FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, PackInfo, PackMember, Params,
+                   PlanesInfo, PlanesRange, check, load)
 
 
 def _buf(data) -> np.ndarray:
@@ -25,6 +25,17 @@ def _buf(data) -> np.ndarray:
 
 def _p(a: np.ndarray):
     return a.ctypes.data_as(C.c_void_p)
+
+
+class PackHead:
+    """What BlockCodec.pack_info reads from a pack frame (fsehip.h section 2j)."""
+
+    def __init__(self, info, members, inner):
+        self.info, self.members, self.inner = info, members, inner
+        n = info.n_members
+        self.kinds = [KINDS[members[m].kind] for m in range(n)]
+        self.elem_bytes = [int(members[m].elem_bytes) for m in range(n)]
+        self.n_elems = [int(members[m].n_elems) for m in range(n)]
 
 
 class _ElemKind:
@@ -1691,6 +1702,8 @@ class BlockCodec:
             raise ValueError("a diff frame decodes against its base: pass base=")
         if kind in _ELEM:
             return self._elem_decompress(kind, buf, dtype, chunk_blocks, base if kind == "diff" else None)
+        if kind == "pack":
+            raise ValueError("a pack frame holds many tensors and goes to decompress_pack")
         if kind != "frame":
             raise ValueError("a sealed buffer goes to decompress_sealed")
         out, status = self.decompress_frame(buf, chunk_blocks)
@@ -1700,6 +1713,209 @@ class BlockCodec:
         if out.numel() == 0:
             return self.torch.empty(0, dtype=dtype, device=self.device), status
         return out.view(dtype), status
+
+    # ---- the pack frame (fsehip.h section 2j): many tensors in one container,
+    # one transform launch over all of them each way around one frame call.
+    # A member is coded as "planes" or "delta" (both at 1-, 2-, 4- and 8-byte
+    # elements); dtypes and shapes stay with the caller.
+    _PACK_KINDS = {"planes": 1, "delta": 2}
+
+    def pack_members(self, tensors, kinds=None):
+        """The fsehip_pack_member array of a list of contiguous device tensors.
+        `kinds`: None (all "planes"), one name or one name per tensor."""
+        n = len(tensors)
+        names = ["planes"] * n if kinds is None else [kinds] * n if isinstance(kinds, str) else list(kinds)
+        if len(names) != n:
+            raise ValueError(f"{len(names)} kinds for {n} tensors")
+        arr = (PackMember * max(n, 1))()
+        for m, (x, kind) in enumerate(zip(tensors, names)):
+            if kind not in self._PACK_KINDS:
+                raise ValueError(f"member kind {kind!r}: a pack takes 'planes' and 'delta' members")
+            if not hasattr(x, "data_ptr") or not x.is_cuda or not x.is_contiguous():
+                raise ValueError(f"member {m}: a pack takes contiguous device tensors")
+            if x.element_size() not in (1, 2, 4, 8):
+                raise ValueError(f"member {m}: element size {x.element_size()}: a pack takes 1, 2, 4 or 8 bytes")
+            arr[m] = PackMember(x.data_ptr() if x.numel() else None, x.numel(), x.element_size(),
+                                self._PACK_KINDS[kind])
+        return arr
+
+    def pack_bound(self, members, n: int) -> int:
+        return int(self.lib.fsehip_pack_bound(members, n, self.block_size))
+
+    def pack_scratch_bytes(self, members, n: int) -> int:
+        return int(self.lib.fsehip_pack_scratch_bytes(members, n))
+
+    def pack_members_scratch_bytes(self, members, n: int, indices) -> int:
+        sel = (C.c_uint32 * max(len(indices), 1))(*indices)
+        return int(self.lib.fsehip_pack_members_scratch_bytes(members, n, sel, len(indices)))
+
+    def _pack_transform_scratch(self, members, n: int):
+        t = self.torch
+        extra = self.pack_scratch_bytes(members, n) - int(self.lib.fsehip_pack_image_bytes(members, n))
+        return t.empty(max(extra, 16), dtype=t.uint8, device=self.device)
+
+    def pack_split(self, tensors, kinds=None):
+        """The pack image of a list of tensors (uint8, pads zeroed): fsehip_pack_split."""
+        t = self.torch
+        members, n = self.pack_members(tensors, kinds), len(tensors)
+        image = t.empty(int(self.lib.fsehip_pack_image_bytes(members, n)), dtype=t.uint8, device=self.device)
+        scratch = self._pack_transform_scratch(members, n)
+        check(self.lib.fsehip_pack_split(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                         scratch.numel(), self._stream()), "fsehip_pack_split")
+        return image
+
+    def pack_merge(self, image, outs, kinds=None):
+        """The members of a pack image into the tensors `outs` (their sizes and dtypes say the list): fsehip_pack_merge."""
+        members, n = self.pack_members(outs, kinds), len(outs)
+        scratch = self._pack_transform_scratch(members, n)
+        check(self.lib.fsehip_pack_merge(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                         scratch.numel(), self._stream()), "fsehip_pack_merge")
+        return outs
+
+    def compress_pack_into(self, members, n: int, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+        """fsehip_pack_compress, no synchronisation: `members` from
+        pack_members, `scratch` a uint8 device tensor of >= pack_scratch_bytes
+        (16-byte aligned), `out` of >= pack_bound bytes, `out_len` one int64,
+        `result` two int32."""
+        p = self._frame_params(chunk_blocks)
+        check(self.lib.fsehip_pack_compress(C.byref(p), members, n, C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                            C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()),
+                                            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_compress")
+
+    def compress_pack(self, tensors, kinds=None, chunk_blocks: int = 0):
+        """Compress a list of contiguous device tensors into one pack frame: a
+        uint8 device tensor of its exact length.  `kinds`: None (all
+        "planes"), one name or one per tensor.  One synchronisation, to read
+        the length."""
+        t = self.torch
+        members, n = self.pack_members(tensors, kinds), len(tensors)
+        bound, need = self.pack_bound(members, n), self.pack_scratch_bytes(members, n)
+        if not bound or not need:
+            raise FseError(-14, "fsehip_pack_bound")
+        scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        out = t.empty(bound, dtype=t.uint8, device=self.device)
+        out_len = t.zeros(1, dtype=t.int64, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.compress_pack_into(members, n, scratch, out, out_len, result, chunk_blocks)
+        return out[: int(out_len.item())]
+
+    @staticmethod
+    def pack_info(buf):
+        """The head of a pack frame given as bytes, a numpy array or a tensor
+        (its 32 + 16 n + 32 head bytes come to the host): a PackHead with
+        `info` (PackInfo), `members` (the PackMember array, pointers null),
+        `inner` (the frame's FrameInfo) and the lists `kinds`, `elem_bytes`
+        and `n_elems`; raises FseError (BAD_FRAME) otherwise."""
+        def take(lo, hi):
+            if hasattr(buf, "data_ptr"):  # a torch tensor
+                return buf[lo:hi].cpu().numpy().tobytes()
+            return bytes(memoryview(buf)[lo:hi])
+
+        lib = load()
+        info, inner = PackInfo(), FrameInfo()
+        a = np.frombuffer(take(0, 32), dtype=np.uint8)
+        check(lib.fsehip_pack_read_header(_p(a), len(a), C.byref(info)), "fsehip_pack_read_header")
+        n = info.n_members
+        a = np.frombuffer(take(0, 32 + 16 * n + 32), dtype=np.uint8)
+        members = (PackMember * max(n, 1))()
+        check(lib.fsehip_pack_read_members(_p(a), len(a), members, n, C.byref(info), C.byref(inner)),
+              "fsehip_pack_read_members")
+        return PackHead(info, members, inner)
+
+    def _pack_outs(self, head, indices, dtypes, outs):
+        """The destinations of the members `indices` after the dtype checks: `outs` or fresh tensors."""
+        t = self.torch
+        dts = [dtypes] * len(indices) if not isinstance(dtypes, (list, tuple)) else list(dtypes)
+        if len(dts) != len(indices):
+            raise ValueError(f"{len(dts)} dtypes for {len(indices)} members")
+        res, widths = [], {}
+        for s, (m, dt) in enumerate(zip(indices, dts)):
+            if not 0 <= m < head.info.n_members:
+                raise ValueError(f"member {m}: the pack holds {head.info.n_members}")
+            w = widths.get(dt) or widths.setdefault(dt, t.empty(0, dtype=dt).element_size())
+            if w != head.elem_bytes[m]:
+                raise ValueError(f"dtype {dt} has {w}-byte elements, member {m} holds {head.elem_bytes[m]}-byte ones")
+            if outs is None:
+                res.append(t.empty(head.n_elems[m], dtype=dt, device=self.device))
+            else:
+                o = outs[s]
+                if not o.is_contiguous() or o.dtype != dt or o.numel() != head.n_elems[m]:
+                    raise ValueError(f"out {s} must be a contiguous tensor of {head.n_elems[m]} elements of {dt}")
+                res.append(o)
+        return res
+
+    @staticmethod
+    def _pack_point(head, indices, outs):
+        """A copy of the head's member array with the members `indices` pointing at `outs`."""
+        n = head.info.n_members
+        members = (PackMember * max(n, 1))()
+        C.memmove(members, head.members, C.sizeof(PackMember) * n)
+        for m, o in zip(indices, outs):
+            members[m].d_ptr = o.data_ptr() if o.numel() else None
+        return members
+
+    def decompress_pack_into(self, buf, head, outs, scratch, block_status, result, chunk_blocks: int = 0) -> None:
+        """fsehip_pack_decompress, no synchronisation: `head` from pack_info,
+        `outs` one contiguous tensor per member (element size and count the
+        table's), `scratch` >= pack_scratch_bytes (16-byte aligned),
+        `block_status` head.inner.n_blocks int32 or None, `result` two int32."""
+        n = head.info.n_members
+        outs = self._pack_outs(head, list(range(n)), [o.dtype for o in outs], outs)
+        members = self._pack_point(head, range(n), outs)
+        check(self.lib.fsehip_pack_decompress(
+            C.byref(head.info), members, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
+            C.c_void_p(scratch.data_ptr()), scratch.numel(),
+            C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_decompress")
+
+    def decompress_pack(self, buf, dtypes, chunk_blocks: int = 0):
+        """Decode a pack frame (a uint8 device tensor) into one 1-D tensor per
+        member; `dtypes` is one dtype or one per member, each of the member's
+        element size (ValueError otherwise).  Returns (tensors, block_status);
+        raises FseError for a frame-level error (BAD_FRAME)."""
+        t = self.torch
+        head = self.pack_info(buf)
+        n = head.info.n_members
+        outs = self._pack_outs(head, list(range(n)), dtypes, None)
+        scratch = t.empty(self.pack_scratch_bytes(head.members, n), dtype=t.uint8, device=self.device)
+        status = t.zeros(head.inner.n_blocks, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_pack_into(buf, head, outs, scratch, status, result, chunk_blocks)
+        check(int(result[0].item()), "pack frame")
+        return outs, status
+
+    def decompress_pack_members_into(self, buf, head, indices, outs, scratch, member_status, result,
+                                     chunk_blocks: int = 0) -> None:
+        """fsehip_pack_decompress_members, no synchronisation: `outs` one
+        tensor per index, `scratch` >= pack_members_scratch_bytes,
+        `member_status` len(indices) int32 or None, `result` two int32."""
+        indices = [int(i) for i in indices]
+        outs = self._pack_outs(head, indices, [o.dtype for o in outs], outs)
+        members = self._pack_point(head, indices, outs)
+        sel = (C.c_uint32 * max(len(indices), 1))(*indices)
+        check(self.lib.fsehip_pack_decompress_members(
+            C.byref(head.info), members, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
+            sel, len(indices), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+            C.c_void_p(member_status.data_ptr()) if member_status is not None else None,
+            C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_decompress_members")
+
+    def decompress_pack_members(self, buf, indices, dtypes, chunk_blocks: int = 0):
+        """Decode only the members `indices` of a pack frame (only the blocks
+        they cover are decoded).  Returns (tensors, member_status); raises
+        FseError for a frame-level error."""
+        t = self.torch
+        head = self.pack_info(buf)
+        indices = [int(i) for i in indices]
+        if len(set(indices)) != len(indices):
+            raise ValueError("a member is selected twice")
+        outs = self._pack_outs(head, indices, dtypes, None)
+        need = self.pack_members_scratch_bytes(head.members, head.info.n_members, indices)
+        scratch = t.empty(max(need, 16), dtype=t.uint8, device=self.device)
+        status = t.zeros(len(indices), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.decompress_pack_members_into(buf, head, indices, outs, scratch, status, result, chunk_blocks)
+        check(int(result[0].item()), "pack frame")
+        return outs, status
 
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
@@ -1843,6 +2059,55 @@ def diff_decompress(data, base, device=None) -> np.ndarray:
 
 
 # ---------------------------------------------------------------- the size estimate and the automatic choice
+def pack_info(buf):
+    """`BlockCodec.pack_info`: the head of a pack frame (fsehip.h section 2j)."""
+    return BlockCodec.pack_info(buf)
+
+
+def pack_compress(arrays, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
+                  nstates: int = 2, device=None) -> bytes:
+    """Compress a list of numpy arrays of item size 1, 2, 4 or 8 into one pack
+    frame on the GPU; copies through torch.  `kinds`: None (all "planes"), one
+    name or one per array.  The element widths are stored, dtypes and shapes
+    are not."""
+    import torch
+
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    tensors = []
+    for m, data in enumerate(arrays):
+        a = np.ascontiguousarray(data)
+        if a.dtype.itemsize not in _INT_VIEW:
+            raise ValueError(f"member {m}: item size {a.dtype.itemsize}: a pack takes 1, 2, 4 or 8 bytes")
+        tensors.append(torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device))
+    return codec.compress_pack(tensors, kinds).cpu().numpy().tobytes()
+
+
+def pack_decompress(blob, dtypes, device=None) -> list:
+    """Decode a pack frame held in host memory into one 1-D numpy array per
+    member; `dtypes` is one dtype or one per member (each of the member's item
+    size); raises FseError on a frame-level error or with the first failed
+    block's status."""
+    import torch
+
+    head = BlockCodec.pack_info(_buf(blob))  # not a pack: BAD_FRAME before any device work
+    n = head.info.n_members
+    dts = [np.dtype(d) for d in (dtypes if isinstance(dtypes, (list, tuple)) else [dtypes] * n)]
+    if len(dts) != n:
+        raise ValueError(f"{len(dts)} dtypes for {n} members")
+    for m, dt in enumerate(dts):
+        if dt.itemsize != head.elem_bytes[m]:
+            raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, member {m} holds {head.elem_bytes[m]}-byte ones")
+    codec = BlockCodec(device=device)
+    buf = torch.from_numpy(_buf(blob).copy()).to(codec.device)
+    outs, status = codec.decompress_pack(buf, [getattr(torch, np.dtype(_INT_VIEW[w]).name) for w in head.elem_bytes])
+    st = status.cpu().numpy()
+    if st.any():
+        b = int(np.flatnonzero(st)[0])
+        raise FseError(int(st[b]), f"pack frame block {b}")
+    return [o.cpu().numpy().view(dt) for o, dt in zip(outs, dts)]
+
+
 def log2q8(c: int) -> int:
     """`fsehip_log2q8`: the estimate's 256 * log2(c) for 1 <= c <= 32768 (host, no device)."""
     if not 1 <= c <= 32768:
@@ -1875,7 +2140,7 @@ def estimate_choose(est):
 
 
 def container_kind(buf) -> str:
-    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed" or "diff" from
+    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed", "diff" or "pack" from
     the magic of a container given as bytes, a numpy array or a tensor (its
     first 4 bytes come to the host); raises FseError (BAD_FRAME) for anything
     else."""
@@ -1887,7 +2152,7 @@ def container_kind(buf) -> str:
     k = load().fsehip_container_kind(_p(a), len(a))
     if k < 0:
         raise FseError(k, "fsehip_container_kind")
-    return "sealed" if k == KIND_SEALED else "diff" if k == KIND_DIFF else KINDS[k]
+    return "sealed" if k == KIND_SEALED else "diff" if k == KIND_DIFF else "pack" if k == KIND_PACK else KINDS[k]
 
 
 def auto_compress(data, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
@@ -1920,6 +2185,8 @@ def auto_decompress(blob, dtype, device=None, base=None) -> np.ndarray:
         raise ValueError("a diff frame decodes against its base: pass base=")
     if kind in _ELEM:
         return _elem_decompress(kind, blob, dtype, device, base if kind == "diff" else None)
+    if kind == "pack":
+        raise ValueError("a pack frame holds many tensors and goes to pack_decompress")
     if kind != "frame":
         raise ValueError("a sealed buffer goes to sealed_decompress")
     return np.frombuffer(frame_decompress(blob, device), dtype=np.dtype(dtype))
@@ -2152,4 +2419,5 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "planes_compress", "planes_decompress", "delta_compress", "delta_decompress", "diff_compress",
            "diff_decompress",
            "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo",
-           "auto_compress", "auto_decompress", "container_kind", "estimate_choose", "log2q8"]
+           "auto_compress", "auto_decompress", "container_kind", "estimate_choose", "log2q8",
+           "pack_compress", "pack_decompress", "pack_info", "PackHead"]

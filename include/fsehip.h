@@ -1553,6 +1553,179 @@ int fsehip_estimate_base(const fsehip_frame_params* p, uint32_t kind_mask, uint3
 int fsehip_estimate_choose_base(const uint64_t est[5]);
 
 /* ------------------------------------------------------------------------
+ * (2j) Pack frames: many tensors in one container, one call each way
+ *
+ * The containers of sections 2b, 2d, 2e and 2h take one tensor per call.  A
+ * checkpoint, a state_dict or a set of CSR arrays is hundreds or thousands of
+ * tensors, most of them small; a caller's loop pays launches, a 48-byte head
+ * and a table header per tensor, and a 2 KiB tensor is one workgroup.  The
+ * pack frame takes the whole list: one transform launch over all members,
+ * one unchanged frame of section 2b over one image, one launch back.  This
+ * library's own container, version 1; integers little-endian, no padding, any
+ * byte address:
+ *
+ *   header, 32 bytes
+ *    0  u8[4] magic "FSEM"
+ *    4  u8    version = 1
+ *    5  u8[3] reserved = 0
+ *    8  u32   n_members       0 .. FSEHIP_PACK_MAX_MEMBERS
+ *   12  u32   reserved = 0
+ *   16  u64   image_bytes     = sum over members of w_m * stride_m (= the inner frame's n_total)
+ *   24  u64   content_bytes   = sum over members of w_m * n_m
+ *   member table, n_members x 16 bytes
+ *    0  u8    kind            FSEHIP_KIND_PLANES or FSEHIP_KIND_DELTA
+ *    1  u8    elem_bytes w    1, 2, 4 or 8 for either kind (planes at w = 1: the bytes themselves)
+ *    2  u8[6] reserved = 0
+ *    8  u64   n_elems         0 is valid
+ *   one frame (section 2b) of the image, to the end of the buffer
+ *
+ * The image.  stride_m = roundup(n_m, 16).  z_m is member m's elements for
+ * the plane kind, and for the delta kind the zigzag deltas of section 2e with
+ * a restart every FSEHIP_DELTA_RESTART elements counted from the member's own
+ * element 0.  Plane k of member m is byte k of every element of z_m: stride_m
+ * bytes, the pad zero.  The image is segments 0..7 back to back, plane-major
+ * from the top byte: segment j holds, for each member with w_m > j in member
+ * order, that member's plane w_m - 1 - j.  So every member's sign/exponent
+ * bytes (or zero high bytes) sit together, then every member's next byte, and
+ * a block's one table never averages a small tensor's exponent plane with its
+ * mantissa plane.  Every plane starts at a multiple of 16.
+ *
+ * A reader rejects (BAD_FRAME) any nonzero reserved byte, another version, a
+ * kind or width outside the lists, n_members above the cap, sums that
+ * overflow or differ from the two header fields, and an inner n_total other
+ * than image_bytes.  "FSEM" is BAD_FRAME to every other reader of this header
+ * (fsehip_sealed_read_header included) and their magics are BAD_FRAME here.
+ *
+ * As the other element frames, the container stores neither names, dtypes,
+ * shapes nor bases.  Diff members (section 2h), a per-member automatic kind
+ * (section 2g) and sealing a pack (section 2f) are out of scope of version 1;
+ * the kind byte and the reserved fields leave room for them.
+ *
+ * A failed inner block costs the elements with a byte in it, and for a delta
+ * member the rest of that restart group as well; BAD_FRAME stores nothing to
+ * any member.
+ * ------------------------------------------------------------------------ */
+#define FSEHIP_KIND_PACK 5u /* section 2j, magic "FSEM": fsehip_container_kind only */
+#define FSEHIP_PACK_MAX_MEMBERS (1u << 20)
+
+/* One member: n_elems elements of elem_bytes at d_ptr (device memory, aligned
+ * to elem_bytes; ignored for n_elems = 0 and by the host calls), coded as
+ * kind.  The encoder reads up to roundup(n_elems * elem_bytes, 4) bytes of
+ * each member at most; the decoders store exactly n_elems * elem_bytes. */
+typedef struct fsehip_pack_member {
+    void* d_ptr;
+    uint64_t n_elems;
+    uint32_t elem_bytes;
+    uint32_t kind;
+} fsehip_pack_member;
+
+typedef struct fsehip_pack_info {
+    uint32_t version;
+    uint32_t n_members;
+    uint64_t image_bytes;
+    uint64_t content_bytes;
+} fsehip_pack_info;
+
+/* Host functions, no device.  A list is valid with at most
+ * FSEHIP_PACK_MAX_MEMBERS members, kinds and widths of the lists above and
+ * sums that fit 64 bits.
+ *  fsehip_pack_image_bytes: the image's size (0 for an invalid list, and for
+ *    one without elements).
+ *  fsehip_pack_bound: an output capacity that holds the pack at that block
+ *    size, 32 + 16 n + fsehip_frame_bound(image); 0 for an invalid list.
+ *  fsehip_pack_scratch_bytes: the scratch of fsehip_pack_compress and
+ *    fsehip_pack_decompress (the image, the members' descriptors, the head);
+ *    minus fsehip_pack_image_bytes: that of the two bare transforms.  0 for an
+ *    invalid list.
+ *  fsehip_pack_members_scratch_bytes: that of fsehip_pack_decompress_members
+ *    for the members sel[0 .. n_sel); 0 for an invalid list or a selection out
+ *    of range.
+ *  fsehip_pack_plane_offset: where byte k of member m's elements lies in the
+ *    image; UINT64_MAX for an invalid list, m or k. */
+uint64_t fsehip_pack_image_bytes(const fsehip_pack_member* members, uint32_t n_members);
+uint64_t fsehip_pack_bound(const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size);
+uint64_t fsehip_pack_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members);
+uint64_t fsehip_pack_members_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, const uint32_t* sel,
+                                           uint32_t n_sel);
+uint64_t fsehip_pack_plane_offset(const fsehip_pack_member* members, uint32_t n_members, uint32_t m, uint32_t k);
+
+/* Host functions, no device.  fsehip_pack_read_header parses the first 32
+ * bytes (the table's length follows from n_members: 16 each); BAD_FRAME and
+ * *out zeroed for fewer bytes or a broken rule.  fsehip_pack_read_members
+ * parses the header, the table and the inner frame's header from the
+ * 32 + 16 n + 32 bytes at buf: members[m] gets kind, elem_bytes and n_elems
+ * (d_ptr null), *out and *inner the two headers; DST_TOO_SMALL when
+ * members_cap is below n_members, BAD_FRAME (outputs zeroed) for every rule
+ * above.  fsehip_pack_write_header writes the 32 + 16 n head bytes of a valid
+ * list (BAD_ARG otherwise). */
+int fsehip_pack_read_header(const uint8_t* buf, size_t len, fsehip_pack_info* out);
+int fsehip_pack_read_members(const uint8_t* buf, size_t len, fsehip_pack_member* members, uint32_t members_cap,
+                             fsehip_pack_info* out, fsehip_frame_info* inner);
+int fsehip_pack_write_header(const fsehip_pack_member* members, uint32_t n_members, uint8_t* out);
+
+/* The bare transforms: every member's elements into the image at d_image
+ * (16-byte aligned, fsehip_pack_image_bytes) and back, one launch for all
+ * members.  d_scratch (16-byte aligned, fsehip_pack_scratch_bytes minus the
+ * image) takes the members' descriptors, which reach the device through the
+ * stream's pinned staging: asynchronous on `stream`, no host synchronisation.
+ * A member's pointer is aligned to its elements, for the split as
+ * fsehip_planes_split; the merge stores at that alignment too (members are
+ * carved from arenas), exactly n_elems * elem_bytes bytes each, and its
+ * destinations must not overlap.  Before any device use: UNSUPPORTED (an
+ * invalid list), BAD_ARG (a null or misaligned pointer with elements,
+ * overlapping destinations), DST_TOO_SMALL (the scratch), NO_DEVICE.  A list
+ * without elements returns FSE_OK and does nothing. */
+int fsehip_pack_split(const fsehip_pack_member* members, uint32_t n_members, uint8_t* d_image, uint8_t* d_scratch,
+                      uint64_t scratch_cap, fsehip_stream_t stream);
+int fsehip_pack_merge(const fsehip_pack_member* members, uint32_t n_members, const uint8_t* d_image,
+                      uint8_t* d_scratch, uint64_t scratch_cap, fsehip_stream_t stream);
+
+/* The pack of the members at d_out: the split, one fsehip_frame_compress of
+ * the image in d_scratch (16-byte aligned, fsehip_pack_scratch_bytes; needed
+ * for an empty list too), then the header and the table written on the
+ * device.  *d_out_len = the pack's bytes, d_result as fsehip_frame_compress.
+ * Asynchronous, no host synchronisation.  Before any device use: BAD_ARG (a
+ * null pointer, a member pointer null or misaligned with elements, the frame
+ * parameters' rules), UNSUPPORTED (an invalid list, a block above the limit),
+ * DST_TOO_SMALL (scratch_cap or out_cap below fsehip_pack_bound), NO_DEVICE. */
+int fsehip_pack_compress(const fsehip_frame_params* p, const fsehip_pack_member* members, uint32_t n_members,
+                         uint8_t* d_scratch, uint64_t scratch_cap, uint8_t* d_out, uint64_t out_cap,
+                         uint64_t* d_out_len, int32_t* d_result, fsehip_stream_t stream);
+
+/* Decode the pack at d_in into the members' destinations: `info`, the
+ * members' fields and `inner` are what fsehip_pack_read_members gave, with
+ * d_ptr set (info->n_members members).  One fsehip_frame_decompress into
+ * d_scratch (fsehip_pack_scratch_bytes), a device check of the 32 + 16 n head
+ * bytes against the caller's, one merge.  d_block_status (may be NULL) and
+ * d_result are the inner frame call's; a head on the device that differs from
+ * the caller's is BAD_FRAME in d_result[0] and every block status, and stores
+ * nothing.  Before any device use: BAD_ARG (a null pointer, members that do
+ * not sum to `info` or `inner`, a destination null, misaligned or overlapping
+ * another), UNSUPPORTED (an invalid list), DST_TOO_SMALL (the scratch),
+ * NO_DEVICE. */
+int fsehip_pack_decompress(const fsehip_pack_info* info, const fsehip_pack_member* members,
+                           const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in, uint64_t in_len,
+                           uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_block_status, int32_t* d_result,
+                           fsehip_stream_t stream);
+
+/* Decode only the members sel[0 .. n_sel) (indices into the list, each once,
+ * any order): their plane ranges go through ONE
+ * fsehip_frame_decompress_ranges call into d_scratch
+ * (fsehip_pack_members_scratch_bytes), so only the blocks they cover are
+ * decoded, then one merge.  Only the selected members need a d_ptr; the
+ * others' destinations are never touched.  d_member_status[s] (may be NULL)
+ * is the status of member sel[s]: its first failing plane range's, FSE_OK for
+ * a member without elements, BAD_FRAME for all on a bad head; d_result[0] is
+ * the frame's status and d_result[1] the members with a status.  Checks as
+ * fsehip_pack_decompress, and BAD_ARG for a selection out of range or named
+ * twice. */
+int fsehip_pack_decompress_members(const fsehip_pack_info* info, const fsehip_pack_member* members,
+                                   const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in,
+                                   uint64_t in_len, const uint32_t* sel, uint32_t n_sel, uint8_t* d_scratch,
+                                   uint64_t scratch_cap, int32_t* d_member_status, int32_t* d_result,
+                                   fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
  *
  * The crate's `pub mod fse` lets a caller code any number of messages against
