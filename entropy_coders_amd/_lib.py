@@ -69,6 +69,10 @@ EXPORTS = (
     "fsehip_pack_plane_offset", "fsehip_pack_read_header", "fsehip_pack_read_members", "fsehip_pack_write_header",
     "fsehip_pack_split", "fsehip_pack_merge", "fsehip_pack_compress", "fsehip_pack_decompress",
     "fsehip_pack_decompress_members",
+    "fsehip_vpack_image_bytes", "fsehip_vpack_bound", "fsehip_vpack_scratch_bytes",
+    "fsehip_vpack_members_scratch_bytes", "fsehip_vpack_plane_offset", "fsehip_vpack_read_header",
+    "fsehip_vpack_read_members", "fsehip_vpack_write_header", "fsehip_vpack_split", "fsehip_vpack_merge",
+    "fsehip_vpack_compress", "fsehip_vpack_decompress", "fsehip_vpack_decompress_members",
 )
 
 STATUS = {
@@ -152,13 +156,14 @@ KINDS = ("frame", "planes", "delta")  # FSEHIP_KIND_FRAME / _PLANES / _DELTA
 KIND_SEALED = 3                        # FSEHIP_KIND_SEALED: fsehip_container_kind of an "FSEK" buffer
 KIND_DIFF = 4                          # FSEHIP_KIND_DIFF: of an "FSEB" buffer; fsehip_estimate_base's fifth entry
 KIND_PACK = 5                          # FSEHIP_KIND_PACK: of an "FSEM" buffer
+KIND_VPACK = 6                         # FSEHIP_KIND_VPACK: of an "FSEV" buffer
 PACK_MAX_MEMBERS = 1 << 20             # FSEHIP_PACK_MAX_MEMBERS
 EST_NONE = (1 << 64) - 1               # FSEHIP_EST_NONE
 EST_RAW, EST_RLE, EST_FSE = 0, 1, 2    # FSEHIP_EST_*: the frame directory's block types
 
 
 class PackMember(C.Structure):
-    """fsehip_pack_member: one tensor of a pack frame; kind is 1 (planes) or 2 (delta)."""
+    """fsehip_pack_member: one tensor of a pack frame; kind is 1 (planes) or 2 (delta), in a versioned pack also 4 (diff)."""
     _fields_ = [("d_ptr", C.c_void_p), ("n_elems", C.c_uint64), ("elem_bytes", C.c_uint32), ("kind", C.c_uint32)]
 
 
@@ -362,6 +367,23 @@ def load() -> C.CDLL:
     lib.fsehip_pack_compress.argtypes = [C.POINTER(FrameParams), PM, u32, P, u64, P, u64, P, P, P]
     lib.fsehip_pack_decompress.argtypes = [PKI, PM, FI, u32, P, u64, P, u64, P, P, P]
     lib.fsehip_pack_decompress_members.argtypes = [PKI, PM, FI, u32, P, u64, C.POINTER(u32), u32, P, u64, P, P, P]
+    # the versioned pack: the same calls, the device ones with the host array of base pointers behind the members
+    BP = C.POINTER(C.c_void_p)
+    for name in ("image_bytes", "bound", "scratch_bytes", "members_scratch_bytes", "plane_offset"):
+        getattr(lib, "fsehip_vpack_" + name).restype = u64
+    lib.fsehip_vpack_image_bytes.argtypes = [PM, u32]
+    lib.fsehip_vpack_bound.argtypes = [PM, u32, u32]
+    lib.fsehip_vpack_scratch_bytes.argtypes = [PM, u32]
+    lib.fsehip_vpack_members_scratch_bytes.argtypes = [PM, u32, C.POINTER(u32), u32]
+    lib.fsehip_vpack_plane_offset.argtypes = [PM, u32, u32, u32]
+    lib.fsehip_vpack_read_header.argtypes = [P, sz, PKI]
+    lib.fsehip_vpack_read_members.argtypes = [P, sz, PM, u32, PKI, FI]
+    lib.fsehip_vpack_write_header.argtypes = [PM, u32, P]
+    lib.fsehip_vpack_split.argtypes = [PM, u32, BP, P, P, u64, P]
+    lib.fsehip_vpack_merge.argtypes = [PM, u32, BP, P, P, u64, P]
+    lib.fsehip_vpack_compress.argtypes = [C.POINTER(FrameParams), PM, u32, BP, P, u64, P, u64, P, P, P]
+    lib.fsehip_vpack_decompress.argtypes = [PKI, PM, BP, FI, u32, P, u64, P, u64, P, P, P]
+    lib.fsehip_vpack_decompress_members.argtypes = [PKI, PM, BP, FI, u32, P, u64, C.POINTER(u32), u32, P, u64, P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

@@ -21,32 +21,6 @@
 
 namespace fsehip {
 
-namespace {
-
-// the inverse of diff_zigzag (fse_planes_dev.hpp): x = b + unzigzag(z) for the
-// N / W * 4 elements of the N dwords z and b (N = 4 W: a group of 16; N = W: a
-// quad of 4)
-template <int W, int N>
-__device__ __forceinline__ void diff_unzigzag(const uint32_t (&z)[N], const uint32_t (&b)[N], uint32_t (&x)[N]) {
-    using A = typename Acc<W>::type;
-    uint32_t ze[4 * W], be[4 * W], xe[4 * W];
-#pragma unroll
-    for (int j = 0; j < 4 * W; ++j) {
-        ze[j] = j < N ? z[j] : 0u;
-        be[j] = j < N ? b[j] : 0u;
-        xe[j] = 0;
-    }
-#pragma unroll
-    for (int i = 0; i < 4 * N / W; ++i) {
-        const A v = get<W>(ze, i);
-        put<W>(xe, i, get<W>(be, i) + ((v >> 1) ^ (A)(0 - (v & 1u))));
-    }
-#pragma unroll
-    for (int j = 0; j < N; ++j) x[j] = xe[j];
-}
-
-}  // namespace
-
 template <int W>
 __global__ __launch_bounds__(PL_T) void diff_split_kernel(const uint8_t* __restrict__ src,
                                                           const uint8_t* __restrict__ base, uint64_t n_elems,

@@ -1,15 +1,19 @@
 // fse_pack.cpp -- the header, member table, sizes and planner of the pack
-// frame, host side (fsehip.h section 2j): 32 header bytes, 16 bytes per
-// member and one frame of section 2b over an image that holds every member's
-// byte planes, plane-major from the top byte.
+// frame and of the versioned pack, host side (fsehip.h sections 2j and 2k): 32
+// header bytes, 16 bytes per member and one frame of section 2b over an image
+// that holds every member's byte planes, plane-major from the top byte.  The
+// two containers are flavours of one implementation: a magic, the member
+// kinds it allows, and whether base pointers travel with the descriptors; the
+// fsehip_pack_* and fsehip_vpack_* entry points are thin fronts of it.
 //
 // Plain C++ with no HIP include, as fse_elem.cpp: the same source builds into
-// libfsehip.so and, with g++ alone, into the sanitizer fuzz of
-// tests/native/pack_fuzz.cpp.  The kernels are fse_pack.hip, the device calls
-// fse_capi_pack.cpp.
+// libfsehip.so and, with g++ alone, into the sanitizer fuzzes of
+// tests/native/pack_fuzz.cpp and vpack_fuzz.cpp.  The kernels are fse_pack.hip
+// and fse_vpack.hip, the device calls fse_capi_pack.cpp.
 #include <string.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "../../include/fsehip.h"
@@ -19,7 +23,10 @@ namespace fsehip {
 
 namespace {
 
-bool kind_ok(uint32_t kind) { return kind == FSEHIP_KIND_PLANES || kind == FSEHIP_KIND_DELTA; }
+const char* magic_of(PackFlavour f) { return f == kFlavourVpack ? "FSEV" : "FSEM"; }
+bool kind_ok(PackFlavour f, uint32_t kind) {
+    return kind == FSEHIP_KIND_PLANES || kind == FSEHIP_KIND_DELTA || (f == kFlavourVpack && kind == FSEHIP_KIND_DIFF);
+}
 bool width_ok(uint32_t w) { return w == 1u || w == 2u || w == 4u || w == 8u; }
 
 // stride = roundup(n_elems, 16); false when it or w * stride overflows
@@ -63,13 +70,14 @@ void fill_desc(const fsehip_pack_member& mb, uint64_t first_tile, PackDesc* d) {
 
 }  // namespace
 
-int pack_geom(const fsehip_pack_member* members, uint64_t n, uint64_t* image_bytes, uint64_t* content_bytes) {
+int pack_geom(const fsehip_pack_member* members, uint64_t n, uint64_t* image_bytes, uint64_t* content_bytes,
+              PackFlavour f) {
     if (n > FSEHIP_PACK_MAX_MEMBERS || (n && !members)) return FSE_ERR_UNSUPPORTED;
     uint64_t image = 0, content = 0;
     for (uint64_t m = 0; m < n; ++m) {
         const uint32_t w = members[m].elem_bytes;
         uint64_t stride;
-        if (!kind_ok(members[m].kind) || !width_ok(w) || !stride_of(members[m].n_elems, w, &stride))
+        if (!kind_ok(f, members[m].kind) || !width_ok(w) || !stride_of(members[m].n_elems, w, &stride))
             return FSE_ERR_UNSUPPORTED;
         if (stride * w > UINT64_MAX - image) return FSE_ERR_UNSUPPORTED;
         image += stride * w;
@@ -142,37 +150,78 @@ int pack_plan_selected(const fsehip_pack_member* members, uint32_t n, const uint
     return FSE_OK;
 }
 
-}  // namespace fsehip
+bool pack_needs_base(const fsehip_pack_member& mb) { return mb.kind == FSEHIP_KIND_DIFF && mb.n_elems != 0; }
 
-using namespace fsehip;
-
-extern "C" {
-
-uint64_t fsehip_pack_image_bytes(const fsehip_pack_member* members, uint32_t n_members) {
-    uint64_t image;
-    return pack_geom(members, n_members, &image, nullptr) == FSE_OK ? image : 0;
+bool pack_bases_ok(const fsehip_pack_member* members, const void* const* bases, const uint32_t* idx, uint32_t n) {
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t m = idx ? idx[i] : i;
+        if (!pack_needs_base(members[m])) continue;
+        if (!bases || !bases[m] || ((uintptr_t)bases[m] & (members[m].elem_bytes - 1u))) return false;
+    }
+    return true;
 }
 
-uint64_t fsehip_pack_bound(const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size) {
+// Sorted destination spans are checked against their neighbours; every base
+// span is then looked up among them by binary search: the one destination it
+// may meet is its own member's, byte for byte.
+bool pack_decode_spans_ok(const fsehip_pack_member* members, const void* const* bases, const uint32_t* idx,
+                          uint32_t n) {
+    struct Span {
+        uintptr_t lo, hi;
+        uint32_t m;
+        bool operator<(const Span& o) const { return lo < o.lo; }
+    };
+    std::vector<Span> dst;
+    dst.reserve(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t m = idx ? idx[i] : i;
+        const fsehip_pack_member& mb = members[m];
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(mb.d_ptr);
+        if (mb.n_elems) dst.push_back(Span{lo, lo + mb.n_elems * mb.elem_bytes, m});
+    }
+    std::sort(dst.begin(), dst.end());
+    for (size_t i = 1; i < dst.size(); ++i)
+        if (dst[i].lo < dst[i - 1].hi) return false;
+    if (!bases) return true;
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t m = idx ? idx[i] : i;
+        if (!pack_needs_base(members[m])) continue;
+        const uintptr_t lo = reinterpret_cast<uintptr_t>(bases[m]), hi = lo + members[m].n_elems * members[m].elem_bytes;
+        // the first destination that ends behind the base's start: the only
+        // candidate's predecessors end at or before it, the spans being disjoint
+        auto it = std::upper_bound(dst.begin(), dst.end(), lo,
+                                   [](uintptr_t v, const Span& s) { return v < s.hi; });
+        if (it == dst.end() || it->lo >= hi) continue;
+        if (it->m != m || it->lo != lo) return false;  // its own destination has its length: no other can meet it
+    }
+    return true;
+}
+
+uint64_t pack_image_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members) {
     uint64_t image;
-    if (pack_geom(members, n_members, &image, nullptr) != FSE_OK) return 0;
+    return pack_geom(members, n_members, &image, nullptr, f) == FSE_OK ? image : 0;
+}
+
+uint64_t pack_bound(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size) {
+    uint64_t image;
+    if (pack_geom(members, n_members, &image, nullptr, f) != FSE_OK) return 0;
     const uint64_t inner = fsehip_frame_bound(image, block_size), head = pack_head_bytes(n_members);
     if (inner < image || inner > UINT64_MAX - head) return 0;  // the frame bound wrapped
     return head + inner;
 }
 
-// the image | the descriptors | the head bytes
-uint64_t fsehip_pack_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members) {
+// the image | the descriptors | the base pointers (the versioned pack) | the head bytes
+uint64_t pack_scratch_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members) {
     uint64_t image;
-    if (pack_geom(members, n_members, &image, nullptr) != FSE_OK) return 0;
-    const uint64_t tail = (sizeof(PackDesc) * (uint64_t)n_members + pack_head_bytes(n_members) + 15u) & ~15ull;
+    if (pack_geom(members, n_members, &image, nullptr, f) != FSE_OK) return 0;
+    const uint64_t tail = (pack_desc_bytes(f) * (uint64_t)n_members + pack_head_bytes(n_members) + 15u) & ~15ull;
     return image > UINT64_MAX - tail ? 0 : image + tail;
 }
 
-// the selected planes | their statuses | the descriptors | the head bytes
-uint64_t fsehip_pack_members_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, const uint32_t* sel,
-                                           uint32_t n_sel) {
-    if (pack_geom(members, n_members, nullptr, nullptr) != FSE_OK || (n_sel && !sel)) return 0;
+// the selected planes | their statuses | the descriptors | the base pointers | the head bytes
+uint64_t pack_members_scratch_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members,
+                                    const uint32_t* sel, uint32_t n_sel) {
+    if (pack_geom(members, n_members, nullptr, nullptr, f) != FSE_OK || (n_sel && !sel)) return 0;
     uint64_t planes = 0, n_planes = 0;
     for (uint32_t s = 0; s < n_sel; ++s) {
         if (sel[s] >= n_members) return 0;
@@ -183,12 +232,13 @@ uint64_t fsehip_pack_members_scratch_bytes(const fsehip_pack_member* members, ui
         n_planes += mb.elem_bytes;
     }
     const uint64_t tail = ((4u * n_planes + 15u) & ~15ull) +
-                          ((sizeof(PackDesc) * (uint64_t)n_sel + pack_head_bytes(n_members) + 15u) & ~15ull);
+                          ((pack_desc_bytes(f) * (uint64_t)n_sel + pack_head_bytes(n_members) + 15u) & ~15ull);
     return planes > UINT64_MAX - tail ? 0 : planes + tail;
 }
 
-uint64_t fsehip_pack_plane_offset(const fsehip_pack_member* members, uint32_t n_members, uint32_t m, uint32_t k) {
-    if (pack_geom(members, n_members, nullptr, nullptr) != FSE_OK || m >= n_members || k >= members[m].elem_bytes)
+uint64_t pack_plane_offset(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint32_t m,
+                           uint32_t k) {
+    if (pack_geom(members, n_members, nullptr, nullptr, f) != FSE_OK || m >= n_members || k >= members[m].elem_bytes)
         return UINT64_MAX;
     const uint32_t j = members[m].elem_bytes - 1u - k;  // the segment
     uint64_t seg[9];
@@ -199,11 +249,11 @@ uint64_t fsehip_pack_plane_offset(const fsehip_pack_member* members, uint32_t n_
     return off;
 }
 
-int fsehip_pack_read_header(const uint8_t* buf, size_t len, fsehip_pack_info* out) {
+int pack_read_header(PackFlavour f, const uint8_t* buf, size_t len, fsehip_pack_info* out) {
     if (!out || (!buf && len)) return FSE_ERR_BAD_ARG;
     memset(out, 0, sizeof(*out));
     if (len < kPackHeaderBytes) return FSE_ERR_BAD_FRAME;
-    if (buf[0] != 'F' || buf[1] != 'S' || buf[2] != 'E' || buf[3] != 'M' || buf[4] != 1u) return FSE_ERR_BAD_FRAME;
+    if (memcmp(buf, magic_of(f), 4) != 0 || buf[4] != 1u) return FSE_ERR_BAD_FRAME;
     for (int i = 5; i < 8; ++i)
         if (buf[i]) return FSE_ERR_BAD_FRAME;
     for (int i = 12; i < 16; ++i)
@@ -219,18 +269,18 @@ int fsehip_pack_read_header(const uint8_t* buf, size_t len, fsehip_pack_info* ou
     return FSE_OK;
 }
 
-int fsehip_pack_read_members(const uint8_t* buf, size_t len, fsehip_pack_member* members, uint32_t members_cap,
-                             fsehip_pack_info* out, fsehip_frame_info* inner) {
+int pack_read_members(PackFlavour f, const uint8_t* buf, size_t len, fsehip_pack_member* members,
+                      uint32_t members_cap, fsehip_pack_info* out, fsehip_frame_info* inner) {
     if (!out || !inner || (!buf && len)) return FSE_ERR_BAD_ARG;
     memset(inner, 0, sizeof(*inner));
-    fsehip_pack_info f;
-    const int rc = fsehip_pack_read_header(buf, len, &f);
+    fsehip_pack_info h;
+    const int rc = pack_read_header(f, buf, len, &h);
     memset(out, 0, sizeof(*out));
     if (rc != FSE_OK) return rc;
-    const uint64_t head = pack_head_bytes(f.n_members);
+    const uint64_t head = pack_head_bytes(h.n_members);
     if (len < head || len - head < 32u) return FSE_ERR_BAD_FRAME;
-    if (f.n_members > members_cap || (f.n_members && !members)) return FSE_ERR_DST_TOO_SMALL;
-    for (uint32_t m = 0; m < f.n_members; ++m) {
+    if (h.n_members > members_cap || (h.n_members && !members)) return FSE_ERR_DST_TOO_SMALL;
+    for (uint32_t m = 0; m < h.n_members; ++m) {
         const uint8_t* e = buf + kPackHeaderBytes + (size_t)kPackEntryBytes * m;
         for (int i = 2; i < 8; ++i)
             if (e[i]) return FSE_ERR_BAD_FRAME;
@@ -240,20 +290,20 @@ int fsehip_pack_read_members(const uint8_t* buf, size_t len, fsehip_pack_member*
         members[m].n_elems = get_u64(e + 8);
     }
     uint64_t image, content;
-    if (pack_geom(members, f.n_members, &image, &content) != FSE_OK) return FSE_ERR_BAD_FRAME;
-    if (image != f.image_bytes || content != f.content_bytes) return FSE_ERR_BAD_FRAME;
+    if (pack_geom(members, h.n_members, &image, &content, f) != FSE_OK) return FSE_ERR_BAD_FRAME;
+    if (image != h.image_bytes || content != h.content_bytes) return FSE_ERR_BAD_FRAME;
     fsehip_frame_info in;
     if (fsehip_frame_read_header(buf + head, len - head, &in) != FSE_OK || in.n_total != image) return FSE_ERR_BAD_FRAME;
-    *out = f;
+    *out = h;
     *inner = in;
     return FSE_OK;
 }
 
-int fsehip_pack_write_header(const fsehip_pack_member* members, uint32_t n_members, uint8_t* out) {
+int pack_write_header(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint8_t* out) {
     uint64_t image, content;
-    if (!out || pack_geom(members, n_members, &image, &content) != FSE_OK) return FSE_ERR_BAD_ARG;
+    if (!out || pack_geom(members, n_members, &image, &content, f) != FSE_OK) return FSE_ERR_BAD_ARG;
     memset(out, 0, kPackHeaderBytes);
-    memcpy(out, "FSEM", 4);
+    memcpy(out, magic_of(f), 4);
     out[4] = 1;
     for (int i = 0; i < 4; ++i) out[8 + i] = (uint8_t)(n_members >> (8 * i));
     put_u64(out + 16, image);
@@ -267,5 +317,45 @@ int fsehip_pack_write_header(const fsehip_pack_member* members, uint32_t n_membe
     }
     return FSE_OK;
 }
+
+}  // namespace fsehip
+
+using namespace fsehip;
+
+// the host calls of both containers: FRONTS(pack, kFlavourPack) are section
+// 2j's, FRONTS(vpack, kFlavourVpack) section 2k's
+#define FSEHIP_PACK_FRONTS(NAME, F)                                                                                 \
+    uint64_t fsehip_##NAME##_image_bytes(const fsehip_pack_member* members, uint32_t n_members) {                   \
+        return pack_image_bytes(F, members, n_members);                                                             \
+    }                                                                                                               \
+    uint64_t fsehip_##NAME##_bound(const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size) {    \
+        return pack_bound(F, members, n_members, block_size);                                                       \
+    }                                                                                                               \
+    uint64_t fsehip_##NAME##_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members) {                 \
+        return pack_scratch_bytes(F, members, n_members);                                                           \
+    }                                                                                                               \
+    uint64_t fsehip_##NAME##_members_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members,           \
+                                                   const uint32_t* sel, uint32_t n_sel) {                           \
+        return pack_members_scratch_bytes(F, members, n_members, sel, n_sel);                                       \
+    }                                                                                                               \
+    uint64_t fsehip_##NAME##_plane_offset(const fsehip_pack_member* members, uint32_t n_members, uint32_t m,        \
+                                          uint32_t k) {                                                             \
+        return pack_plane_offset(F, members, n_members, m, k);                                                      \
+    }                                                                                                               \
+    int fsehip_##NAME##_read_header(const uint8_t* buf, size_t len, fsehip_pack_info* out) {                        \
+        return pack_read_header(F, buf, len, out);                                                                  \
+    }                                                                                                               \
+    int fsehip_##NAME##_read_members(const uint8_t* buf, size_t len, fsehip_pack_member* members,                   \
+                                     uint32_t members_cap, fsehip_pack_info* out, fsehip_frame_info* inner) {       \
+        return pack_read_members(F, buf, len, members, members_cap, out, inner);                                    \
+    }                                                                                                               \
+    int fsehip_##NAME##_write_header(const fsehip_pack_member* members, uint32_t n_members, uint8_t* out) {         \
+        return pack_write_header(F, members, n_members, out);                                                       \
+    }
+
+extern "C" {
+
+FSEHIP_PACK_FRONTS(pack, kFlavourPack)
+FSEHIP_PACK_FRONTS(vpack, kFlavourVpack)
 
 }  // extern "C"

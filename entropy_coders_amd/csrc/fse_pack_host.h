@@ -1,10 +1,11 @@
-// fse_pack_host.h -- what the pack frame's translation units share (fsehip.h
-// section 2j): the device descriptor of one member, the planner of
-// fse_pack.cpp that fills it, and the launchers of fse_pack.hip, called by
-// fse_capi_pack.cpp.  Plain C++ with no HIP include (a stream travels as
+// fse_pack_host.h -- what the translation units of the pack frame and of the
+// versioned pack share (fsehip.h sections 2j and 2k): the device descriptor
+// of one member, the planner of fse_pack.cpp that fills it, and the launchers
+// of fse_pack.hip and fse_vpack.hip, called by fse_capi_pack.cpp.  Plain C++ with no HIP include (a stream travels as
 // void*), so that fse_pack.cpp builds with g++ alone.  Not part of the public
 // ABI.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include <vector>
@@ -35,10 +36,46 @@ static_assert(sizeof(PackDesc) == 104, "uploaded as bytes");
 
 inline uint64_t pack_head_bytes(uint64_t n) { return kPackHeaderBytes + kPackEntryBytes * n; }
 
+// The two containers over this code: the pack frame (magic "FSEM", planes and
+// delta members) and the versioned pack ("FSEV", diff members as well, whose
+// base pointers travel behind the descriptors as one uint64_t per member).
+enum PackFlavour { kFlavourPack = 0, kFlavourVpack = 1 };
+
+// per member, what reaches the device: the descriptor, and a base pointer in the versioned pack
+inline uint64_t pack_desc_bytes(PackFlavour f) { return sizeof(PackDesc) + (f == kFlavourVpack ? 8u : 0u); }
+
 // FSE_OK and the two sums of a member list, or UNSUPPORTED: more members than
-// FSEHIP_PACK_MAX_MEMBERS, a kind or width outside the lists, a sum that
-// overflows.  Pointers are not looked at.
-int pack_geom(const fsehip_pack_member* members, uint64_t n, uint64_t* image_bytes, uint64_t* content_bytes);
+// FSEHIP_PACK_MAX_MEMBERS, a kind or width outside the flavour's lists, a sum
+// that overflows.  Pointers are not looked at.
+int pack_geom(const fsehip_pack_member* members, uint64_t n, uint64_t* image_bytes, uint64_t* content_bytes,
+              PackFlavour f = kFlavourPack);
+
+// the host calls of either container: fsehip_pack_* and fsehip_vpack_* are fronts of these
+uint64_t pack_image_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members);
+uint64_t pack_bound(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size);
+uint64_t pack_scratch_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members);
+uint64_t pack_members_scratch_bytes(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members,
+                                    const uint32_t* sel, uint32_t n_sel);
+uint64_t pack_plane_offset(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint32_t m,
+                           uint32_t k);
+int pack_read_header(PackFlavour f, const uint8_t* buf, size_t len, fsehip_pack_info* out);
+int pack_read_members(PackFlavour f, const uint8_t* buf, size_t len, fsehip_pack_member* members,
+                      uint32_t members_cap, fsehip_pack_info* out, fsehip_frame_info* inner);
+int pack_write_header(PackFlavour f, const fsehip_pack_member* members, uint32_t n_members, uint8_t* out);
+
+// The pointer checks of the versioned pack's device calls, over the members
+// idx[0 .. n) of a valid list (idx nullptr: all n); members without elements
+// take no part, and a base counts for a diff member only.
+// a diff member with elements
+bool pack_needs_base(const fsehip_pack_member& mb);
+// every such member's base is there and aligned to its elements (bases may be nullptr when there is none)
+bool pack_bases_ok(const fsehip_pack_member* members, const void* const* bases, const uint32_t* idx, uint32_t n);
+// The decode side: no destination shares a byte with another destination, nor
+// with the base of a diff member, except that a diff member's destination may
+// be its base itself (the in-place update).  O(n log n).  bases nullptr: the
+// destinations alone.
+bool pack_decode_spans_ok(const fsehip_pack_member* members, const void* const* bases, const uint32_t* idx,
+                          uint32_t n);
 
 // The descriptors of a valid list with plane offsets into the image; returns the tile count.
 uint64_t pack_plan(const fsehip_pack_member* members, uint32_t n, PackDesc* out);
@@ -58,6 +95,12 @@ int launch_pack_split(const PackDesc* d_descs, uint32_t n, uint64_t tiles, uint8
 // `result`: the frame-status word (nullptr: none); BAD_FRAME there stores nothing
 int launch_pack_merge(const PackDesc* d_descs, uint32_t n, uint64_t tiles, const uint8_t* planes,
                       const int32_t* result, void* stream);
+// The versioned pack's transforms (fse_vpack.hip): as the two above, with
+// d_bases[m] the base of member m's descriptor (read for diff members only).
+int launch_vpack_split(const PackDesc* d_descs, const uint64_t* d_bases, uint32_t n, uint64_t tiles, uint8_t* image,
+                       void* stream);
+int launch_vpack_merge(const PackDesc* d_descs, const uint64_t* d_bases, uint32_t n, uint64_t tiles,
+                       const uint8_t* planes, const int32_t* result, void* stream);
 // encode: the head bytes at d_head to `out`, *out_len += head_bytes
 int launch_pack_finish(const uint8_t* d_head, uint64_t head_bytes, uint8_t* out, uint64_t* out_len, void* stream);
 // decode, after the frame call: the head bytes at `in` against d_head; on a

@@ -11,7 +11,7 @@ import threading
 
 import numpy as np
 
-from ._lib import (EST_NONE, KIND_DIFF, KIND_PACK, KIND_SEALED, KINDS, SEALED_KINDS, BitStackReaderState,
+from ._lib import (EST_NONE, KIND_DIFF, KIND_PACK, KIND_SEALED, KIND_VPACK, KINDS, SEALED_KINDS, BitStackReaderState,
                    BitStackWriterState, BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, DiffInfo, EncodeTable,
                    FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, PackInfo, PackMember, Params,
                    PlanesInfo, PlanesRange, check, load)
@@ -28,14 +28,19 @@ def _p(a: np.ndarray):
 
 
 class PackHead:
-    """What BlockCodec.pack_info reads from a pack frame (fsehip.h section 2j)."""
+    """What BlockCodec.pack_info reads from a pack frame (fsehip.h section
+    2j) or a versioned pack (section 2k): `container` says which, "pack" or
+    "vpack"; only the latter's `kinds` may hold "diff"."""
 
-    def __init__(self, info, members, inner):
-        self.info, self.members, self.inner = info, members, inner
+    def __init__(self, info, members, inner, container="pack"):
+        self.info, self.members, self.inner, self.container = info, members, inner, container
         n = info.n_members
-        self.kinds = [KINDS[members[m].kind] for m in range(n)]
+        self.kinds = [_PACK_KIND_NAMES[members[m].kind] for m in range(n)]
         self.elem_bytes = [int(members[m].elem_bytes) for m in range(n)]
         self.n_elems = [int(members[m].n_elems) for m in range(n)]
+
+
+_PACK_KIND_NAMES = {1: "planes", 2: "delta", KIND_DIFF: "diff"}
 
 
 class _ElemKind:
@@ -1702,7 +1707,7 @@ class BlockCodec:
             raise ValueError("a diff frame decodes against its base: pass base=")
         if kind in _ELEM:
             return self._elem_decompress(kind, buf, dtype, chunk_blocks, base if kind == "diff" else None)
-        if kind == "pack":
+        if kind in ("pack", "vpack"):
             raise ValueError("a pack frame holds many tensors and goes to decompress_pack")
         if kind != "frame":
             raise ValueError("a sealed buffer goes to decompress_sealed")
@@ -1718,94 +1723,171 @@ class BlockCodec:
     # one transform launch over all of them each way around one frame call.
     # A member is coded as "planes" or "delta" (both at 1-, 2-, 4- and 8-byte
     # elements); dtypes and shapes stay with the caller.
+    #
+    # With bases= the same calls write and read the versioned pack (section
+    # 2k): a member with a base may be coded as "diff", its zigzag difference
+    # against the base tensor.  THE CONTAINER DOES NOT IDENTIFY ITS BASES.
     _PACK_KINDS = {"planes": 1, "delta": 2}
+    _VPACK_KINDS = {"planes": 1, "delta": 2, "diff": KIND_DIFF}
 
-    def pack_members(self, tensors, kinds=None):
+    def _pack_fn(self, name: str, versioned: bool):
+        return getattr(self.lib, ("fsehip_vpack_" if versioned else "fsehip_pack_") + name)
+
+    def pack_bases(self, tensors, bases, kinds=None):
+        """The kinds and the host array of base pointers of a versioned pack's
+        list: `bases` one entry per tensor, None or a contiguous device tensor
+        of the tensor's element size and count.  `kinds`: None ("diff" where a
+        base is given, "planes" where not), one name or one per tensor; "diff"
+        without a base is a ValueError.  Returns (names, pointer array)."""
+        n = len(tensors)
+        bases = list(bases)
+        if len(bases) != n:
+            raise ValueError(f"{len(bases)} bases for {n} tensors")
+        if kinds is None:
+            names = ["planes" if b is None else "diff" for b in bases]
+        else:
+            names = [kinds] * n if isinstance(kinds, str) else list(kinds)
+        if len(names) != n:
+            raise ValueError(f"{len(names)} kinds for {n} tensors")
+        arr = (C.c_void_p * max(n, 1))()
+        for m, (x, b, kind) in enumerate(zip(tensors, bases, names)):
+            if kind == "diff" and b is None:
+                raise ValueError(f"member {m}: a 'diff' member needs its base")
+            if b is None:
+                continue
+            if not hasattr(b, "data_ptr") or not b.is_cuda or not b.is_contiguous():
+                raise ValueError(f"base {m}: a versioned pack takes contiguous device tensors")
+            if b.element_size() != x.element_size() or b.numel() != x.numel():
+                raise ValueError(f"base {m}: {b.numel()} elements of {b.element_size()} bytes against "
+                                 f"{x.numel()} of {x.element_size()}")
+            arr[m] = b.data_ptr() if b.numel() else None
+        return names, arr
+
+    def pack_members(self, tensors, kinds=None, versioned: bool = False):
         """The fsehip_pack_member array of a list of contiguous device tensors.
-        `kinds`: None (all "planes"), one name or one name per tensor."""
+        `kinds`: None (all "planes"), one name or one name per tensor;
+        `versioned`: the list of a versioned pack, which also takes "diff"."""
         n = len(tensors)
         names = ["planes"] * n if kinds is None else [kinds] * n if isinstance(kinds, str) else list(kinds)
         if len(names) != n:
             raise ValueError(f"{len(names)} kinds for {n} tensors")
         arr = (PackMember * max(n, 1))()
+        known = self._VPACK_KINDS if versioned else self._PACK_KINDS
         for m, (x, kind) in enumerate(zip(tensors, names)):
-            if kind not in self._PACK_KINDS:
+            if kind not in known:
+                if versioned:
+                    raise ValueError(f"member kind {kind!r}: a versioned pack takes 'planes', 'delta' and 'diff' members")
                 raise ValueError(f"member kind {kind!r}: a pack takes 'planes' and 'delta' members")
             if not hasattr(x, "data_ptr") or not x.is_cuda or not x.is_contiguous():
                 raise ValueError(f"member {m}: a pack takes contiguous device tensors")
             if x.element_size() not in (1, 2, 4, 8):
                 raise ValueError(f"member {m}: element size {x.element_size()}: a pack takes 1, 2, 4 or 8 bytes")
-            arr[m] = PackMember(x.data_ptr() if x.numel() else None, x.numel(), x.element_size(),
-                                self._PACK_KINDS[kind])
+            arr[m] = PackMember(x.data_ptr() if x.numel() else None, x.numel(), x.element_size(), known[kind])
         return arr
 
-    def pack_bound(self, members, n: int) -> int:
-        return int(self.lib.fsehip_pack_bound(members, n, self.block_size))
+    def pack_bound(self, members, n: int, versioned: bool = False) -> int:
+        return int(self._pack_fn("bound", versioned)(members, n, self.block_size))
 
-    def pack_scratch_bytes(self, members, n: int) -> int:
-        return int(self.lib.fsehip_pack_scratch_bytes(members, n))
+    def pack_scratch_bytes(self, members, n: int, versioned: bool = False) -> int:
+        return int(self._pack_fn("scratch_bytes", versioned)(members, n))
 
-    def pack_members_scratch_bytes(self, members, n: int, indices) -> int:
+    def pack_members_scratch_bytes(self, members, n: int, indices, versioned: bool = False) -> int:
         sel = (C.c_uint32 * max(len(indices), 1))(*indices)
-        return int(self.lib.fsehip_pack_members_scratch_bytes(members, n, sel, len(indices)))
+        return int(self._pack_fn("members_scratch_bytes", versioned)(members, n, sel, len(indices)))
 
-    def _pack_transform_scratch(self, members, n: int):
+    def _pack_transform_scratch(self, members, n: int, versioned: bool = False):
         t = self.torch
-        extra = self.pack_scratch_bytes(members, n) - int(self.lib.fsehip_pack_image_bytes(members, n))
+        extra = self.pack_scratch_bytes(members, n, versioned) - int(self._pack_fn("image_bytes", versioned)(members, n))
         return t.empty(max(extra, 16), dtype=t.uint8, device=self.device)
 
-    def pack_split(self, tensors, kinds=None):
-        """The pack image of a list of tensors (uint8, pads zeroed): fsehip_pack_split."""
+    def pack_split(self, tensors, kinds=None, bases=None):
+        """The pack image of a list of tensors (uint8, pads zeroed):
+        fsehip_pack_split; with `bases` (pack_bases) the versioned pack's,
+        fsehip_vpack_split."""
         t = self.torch
-        members, n = self.pack_members(tensors, kinds), len(tensors)
-        image = t.empty(int(self.lib.fsehip_pack_image_bytes(members, n)), dtype=t.uint8, device=self.device)
-        scratch = self._pack_transform_scratch(members, n)
-        check(self.lib.fsehip_pack_split(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                         scratch.numel(), self._stream()), "fsehip_pack_split")
+        n, versioned = len(tensors), bases is not None
+        if versioned:
+            kinds, barr = self.pack_bases(tensors, bases, kinds)
+        members = self.pack_members(tensors, kinds, versioned)
+        image = t.empty(int(self._pack_fn("image_bytes", versioned)(members, n)), dtype=t.uint8, device=self.device)
+        scratch = self._pack_transform_scratch(members, n, versioned)
+        if versioned:
+            check(self.lib.fsehip_vpack_split(members, n, barr, C.c_void_p(image.data_ptr()),
+                                              C.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream()),
+                  "fsehip_vpack_split")
+        else:
+            check(self.lib.fsehip_pack_split(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                             scratch.numel(), self._stream()), "fsehip_pack_split")
         return image
 
-    def pack_merge(self, image, outs, kinds=None):
-        """The members of a pack image into the tensors `outs` (their sizes and dtypes say the list): fsehip_pack_merge."""
-        members, n = self.pack_members(outs, kinds), len(outs)
-        scratch = self._pack_transform_scratch(members, n)
-        check(self.lib.fsehip_pack_merge(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
-                                         scratch.numel(), self._stream()), "fsehip_pack_merge")
+    def pack_merge(self, image, outs, kinds=None, bases=None):
+        """The members of a pack image into the tensors `outs` (their sizes
+        and dtypes say the list): fsehip_pack_merge; with `bases` the
+        versioned pack's, fsehip_vpack_merge (an out may be its base itself)."""
+        n, versioned = len(outs), bases is not None
+        if versioned:
+            kinds, barr = self.pack_bases(outs, bases, kinds)
+        members = self.pack_members(outs, kinds, versioned)
+        scratch = self._pack_transform_scratch(members, n, versioned)
+        if versioned:
+            check(self.lib.fsehip_vpack_merge(members, n, barr, C.c_void_p(image.data_ptr()),
+                                              C.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream()),
+                  "fsehip_vpack_merge")
+        else:
+            check(self.lib.fsehip_pack_merge(members, n, C.c_void_p(image.data_ptr()), C.c_void_p(scratch.data_ptr()),
+                                             scratch.numel(), self._stream()), "fsehip_pack_merge")
         return outs
 
-    def compress_pack_into(self, members, n: int, scratch, out, out_len, result, chunk_blocks: int = 0) -> None:
+    def compress_pack_into(self, members, n: int, scratch, out, out_len, result, chunk_blocks: int = 0,
+                           bases=None) -> None:
         """fsehip_pack_compress, no synchronisation: `members` from
         pack_members, `scratch` a uint8 device tensor of >= pack_scratch_bytes
         (16-byte aligned), `out` of >= pack_bound bytes, `out_len` one int64,
-        `result` two int32."""
+        `result` two int32.  `bases`: the pointer array of pack_bases, with
+        the members, scratch and bound of a versioned pack:
+        fsehip_vpack_compress."""
         p = self._frame_params(chunk_blocks)
+        if bases is not None:
+            check(self.lib.fsehip_vpack_compress(C.byref(p), members, n, bases, C.c_void_p(scratch.data_ptr()),
+                                                 scratch.numel(), C.c_void_p(out.data_ptr()), out.numel(),
+                                                 C.c_void_p(out_len.data_ptr()), C.c_void_p(result.data_ptr()),
+                                                 self._stream()), "fsehip_vpack_compress")
+            return
         check(self.lib.fsehip_pack_compress(C.byref(p), members, n, C.c_void_p(scratch.data_ptr()), scratch.numel(),
                                             C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()),
                                             C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_compress")
 
-    def compress_pack(self, tensors, kinds=None, chunk_blocks: int = 0):
+    def compress_pack(self, tensors, kinds=None, chunk_blocks: int = 0, bases=None):
         """Compress a list of contiguous device tensors into one pack frame: a
         uint8 device tensor of its exact length.  `kinds`: None (all
-        "planes"), one name or one per tensor.  One synchronisation, to read
-        the length."""
+        "planes"), one name or one per tensor.  With `bases` (one entry per
+        tensor: None, or a contiguous device tensor of the same element size
+        and count) the output is a versioned pack, and the kinds default to
+        "diff" where a base is given and "planes" where not.  One
+        synchronisation, to read the length."""
         t = self.torch
-        members, n = self.pack_members(tensors, kinds), len(tensors)
-        bound, need = self.pack_bound(members, n), self.pack_scratch_bytes(members, n)
+        n, versioned, barr = len(tensors), bases is not None, None
+        if versioned:
+            kinds, barr = self.pack_bases(tensors, bases, kinds)
+        members = self.pack_members(tensors, kinds, versioned)
+        bound, need = self.pack_bound(members, n, versioned), self.pack_scratch_bytes(members, n, versioned)
         if not bound or not need:
             raise FseError(-14, "fsehip_pack_bound")
         scratch = t.empty(need, dtype=t.uint8, device=self.device)
         out = t.empty(bound, dtype=t.uint8, device=self.device)
         out_len = t.zeros(1, dtype=t.int64, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.compress_pack_into(members, n, scratch, out, out_len, result, chunk_blocks)
+        self.compress_pack_into(members, n, scratch, out, out_len, result, chunk_blocks, barr)
         return out[: int(out_len.item())]
 
     @staticmethod
     def pack_info(buf):
-        """The head of a pack frame given as bytes, a numpy array or a tensor
-        (its 32 + 16 n + 32 head bytes come to the host): a PackHead with
-        `info` (PackInfo), `members` (the PackMember array, pointers null),
-        `inner` (the frame's FrameInfo) and the lists `kinds`, `elem_bytes`
-        and `n_elems`; raises FseError (BAD_FRAME) otherwise."""
+        """The head of a pack frame or a versioned pack given as bytes, a
+        numpy array or a tensor (its 32 + 16 n + 32 head bytes come to the
+        host): a PackHead with `info` (PackInfo), `members` (the PackMember
+        array, pointers null), `inner` (the frame's FrameInfo), the lists
+        `kinds`, `elem_bytes` and `n_elems`, and `container`, "pack" or
+        "vpack"; raises FseError (BAD_FRAME) otherwise."""
         def take(lo, hi):
             if hasattr(buf, "data_ptr"):  # a torch tensor
                 return buf[lo:hi].cpu().numpy().tobytes()
@@ -1814,13 +1896,15 @@ class BlockCodec:
         lib = load()
         info, inner = PackInfo(), FrameInfo()
         a = np.frombuffer(take(0, 32), dtype=np.uint8)
-        check(lib.fsehip_pack_read_header(_p(a), len(a), C.byref(info)), "fsehip_pack_read_header")
+        versioned = lib.fsehip_container_kind(_p(a), len(a)) == KIND_VPACK
+        prefix = "fsehip_vpack_" if versioned else "fsehip_pack_"
+        check(getattr(lib, prefix + "read_header")(_p(a), len(a), C.byref(info)), prefix + "read_header")
         n = info.n_members
         a = np.frombuffer(take(0, 32 + 16 * n + 32), dtype=np.uint8)
         members = (PackMember * max(n, 1))()
-        check(lib.fsehip_pack_read_members(_p(a), len(a), members, n, C.byref(info), C.byref(inner)),
-              "fsehip_pack_read_members")
-        return PackHead(info, members, inner)
+        check(getattr(lib, prefix + "read_members")(_p(a), len(a), members, n, C.byref(info), C.byref(inner)),
+              prefix + "read_members")
+        return PackHead(info, members, inner, "vpack" if versioned else "pack")
 
     def _pack_outs(self, head, indices, dtypes, outs):
         """The destinations of the members `indices` after the dtype checks: `outs` or fresh tensors."""
@@ -1854,66 +1938,131 @@ class BlockCodec:
             members[m].d_ptr = o.data_ptr() if o.numel() else None
         return members
 
-    def decompress_pack_into(self, buf, head, outs, scratch, block_status, result, chunk_blocks: int = 0) -> None:
+    def _pack_decode_bases(self, head, indices, bases):
+        """The host array of base pointers (one per member of the pack) for a
+        decode of the members `indices` of a versioned pack: `bases` a list
+        with one entry per index or a dict by member index, None where a
+        member has no base; every selected diff member needs one."""
+        n = head.info.n_members
+        if bases is None:
+            given = {}
+        elif isinstance(bases, dict):
+            given = {int(m): b for m, b in bases.items() if b is not None}
+        else:
+            bases = list(bases)
+            if len(bases) != len(indices):
+                raise ValueError(f"{len(bases)} bases for {len(indices)} members")
+            given = {m: b for m, b in zip(indices, bases) if b is not None}
+        arr = (C.c_void_p * max(n, 1))()
+        for m in indices:
+            b = given.get(m)
+            if b is None:
+                if head.kinds[m] == "diff":
+                    raise ValueError(f"member {m} is a diff member and decodes against its base: pass bases=")
+                continue
+            if not hasattr(b, "data_ptr") or not b.is_cuda or not b.is_contiguous():
+                raise ValueError(f"base {m}: a versioned pack takes contiguous device tensors")
+            if b.element_size() != head.elem_bytes[m] or b.numel() != head.n_elems[m]:
+                raise ValueError(f"base {m}: {b.numel()} elements of {b.element_size()} bytes, member {m} holds "
+                                 f"{head.n_elems[m]} of {head.elem_bytes[m]}")
+            arr[m] = b.data_ptr() if b.numel() else None
+        return arr
+
+    def decompress_pack_into(self, buf, head, outs, scratch, block_status, result, chunk_blocks: int = 0,
+                             bases=None) -> None:
         """fsehip_pack_decompress, no synchronisation: `head` from pack_info,
         `outs` one contiguous tensor per member (element size and count the
         table's), `scratch` >= pack_scratch_bytes (16-byte aligned),
-        `block_status` head.inner.n_blocks int32 or None, `result` two int32."""
+        `block_status` head.inner.n_blocks int32 or None, `result` two int32.
+        A versioned pack (fsehip_vpack_decompress; its scratch is
+        pack_scratch_bytes(..., versioned=True)) takes `bases`, one entry per
+        member or a dict by index; an out may be its base itself."""
         n = head.info.n_members
         outs = self._pack_outs(head, list(range(n)), [o.dtype for o in outs], outs)
         members = self._pack_point(head, range(n), outs)
+        if head.container == "vpack":
+            barr = self._pack_decode_bases(head, list(range(n)), bases)
+            check(self.lib.fsehip_vpack_decompress(
+                C.byref(head.info), members, barr, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()),
+                buf.numel(), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
+                C.c_void_p(result.data_ptr()), self._stream()), "fsehip_vpack_decompress")
+            return
         check(self.lib.fsehip_pack_decompress(
             C.byref(head.info), members, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
             C.c_void_p(scratch.data_ptr()), scratch.numel(),
             C.c_void_p(block_status.data_ptr()) if block_status is not None else None,
             C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_decompress")
 
-    def decompress_pack(self, buf, dtypes, chunk_blocks: int = 0):
-        """Decode a pack frame (a uint8 device tensor) into one 1-D tensor per
-        member; `dtypes` is one dtype or one per member, each of the member's
-        element size (ValueError otherwise).  Returns (tensors, block_status);
+    def decompress_pack(self, buf, dtypes, chunk_blocks: int = 0, bases=None, outs=None):
+        """Decode a pack frame or a versioned pack (a uint8 device tensor)
+        into one 1-D tensor per member; `dtypes` is one dtype or one per
+        member, each of the member's element size (ValueError otherwise).
+        A versioned pack with diff members needs `bases` (one entry per
+        member, None where there is none; ValueError without).  `outs`: the
+        destinations, fresh tensors by default; outs=bases, or the same
+        tensors in both, decodes in place.  Returns (tensors, block_status);
         raises FseError for a frame-level error (BAD_FRAME)."""
         t = self.torch
         head = self.pack_info(buf)
-        n = head.info.n_members
-        outs = self._pack_outs(head, list(range(n)), dtypes, None)
-        scratch = t.empty(self.pack_scratch_bytes(head.members, n), dtype=t.uint8, device=self.device)
+        n, versioned = head.info.n_members, head.container == "vpack"
+        if versioned:
+            self._pack_decode_bases(head, list(range(n)), bases)  # the argument errors, ahead of any allocation
+        outs = self._pack_outs(head, list(range(n)), dtypes, outs)
+        scratch = t.empty(self.pack_scratch_bytes(head.members, n, versioned), dtype=t.uint8, device=self.device)
         status = t.zeros(head.inner.n_blocks, dtype=t.int32, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_pack_into(buf, head, outs, scratch, status, result, chunk_blocks)
+        self.decompress_pack_into(buf, head, outs, scratch, status, result, chunk_blocks, bases)
         check(int(result[0].item()), "pack frame")
         return outs, status
 
     def decompress_pack_members_into(self, buf, head, indices, outs, scratch, member_status, result,
-                                     chunk_blocks: int = 0) -> None:
+                                     chunk_blocks: int = 0, bases=None) -> None:
         """fsehip_pack_decompress_members, no synchronisation: `outs` one
         tensor per index, `scratch` >= pack_members_scratch_bytes,
-        `member_status` len(indices) int32 or None, `result` two int32."""
+        `member_status` len(indices) int32 or None, `result` two int32.  A
+        versioned pack (fsehip_vpack_decompress_members) takes `bases`, a list
+        with one entry per index or a dict by member index: the selected diff
+        members' are needed."""
         indices = [int(i) for i in indices]
         outs = self._pack_outs(head, indices, [o.dtype for o in outs], outs)
         members = self._pack_point(head, indices, outs)
         sel = (C.c_uint32 * max(len(indices), 1))(*indices)
+        if head.container == "vpack":
+            barr = self._pack_decode_bases(head, indices, bases)
+            check(self.lib.fsehip_vpack_decompress_members(
+                C.byref(head.info), members, barr, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()),
+                buf.numel(), sel, len(indices), C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                C.c_void_p(member_status.data_ptr()) if member_status is not None else None,
+                C.c_void_p(result.data_ptr()), self._stream()), "fsehip_vpack_decompress_members")
+            return
         check(self.lib.fsehip_pack_decompress_members(
             C.byref(head.info), members, C.byref(head.inner), chunk_blocks, C.c_void_p(buf.data_ptr()), buf.numel(),
             sel, len(indices), C.c_void_p(scratch.data_ptr()), scratch.numel(),
             C.c_void_p(member_status.data_ptr()) if member_status is not None else None,
             C.c_void_p(result.data_ptr()), self._stream()), "fsehip_pack_decompress_members")
 
-    def decompress_pack_members(self, buf, indices, dtypes, chunk_blocks: int = 0):
-        """Decode only the members `indices` of a pack frame (only the blocks
-        they cover are decoded).  Returns (tensors, member_status); raises
-        FseError for a frame-level error."""
+    def decompress_pack_members(self, buf, indices, dtypes, chunk_blocks: int = 0, bases=None, outs=None):
+        """Decode only the members `indices` of a pack frame or a versioned
+        pack (only the blocks they cover are decoded).  `bases`: a list with
+        one entry per index or a dict by member index, covering the selected
+        diff members of a versioned pack; `outs`: the destinations, fresh
+        tensors by default.  Returns (tensors, member_status); raises FseError
+        for a frame-level error."""
         t = self.torch
         head = self.pack_info(buf)
         indices = [int(i) for i in indices]
         if len(set(indices)) != len(indices):
             raise ValueError("a member is selected twice")
-        outs = self._pack_outs(head, indices, dtypes, None)
-        need = self.pack_members_scratch_bytes(head.members, head.info.n_members, indices)
+        versioned = head.container == "vpack"
+        outs = self._pack_outs(head, indices, dtypes, outs)
+        if versioned:
+            self._pack_decode_bases(head, indices, bases)
+        need = self.pack_members_scratch_bytes(head.members, head.info.n_members, indices, versioned)
         scratch = t.empty(max(need, 16), dtype=t.uint8, device=self.device)
         status = t.zeros(len(indices), dtype=t.int32, device=self.device)
         result = t.zeros(2, dtype=t.int32, device=self.device)
-        self.decompress_pack_members_into(buf, head, indices, outs, scratch, status, result, chunk_blocks)
+        self.decompress_pack_members_into(buf, head, indices, outs, scratch, status, result, chunk_blocks, bases)
         check(int(result[0].item()), "pack frame")
         return outs, status
 
@@ -2064,30 +2213,44 @@ def pack_info(buf):
     return BlockCodec.pack_info(buf)
 
 
-def pack_compress(arrays, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
-                  nstates: int = 2, device=None) -> bytes:
-    """Compress a list of numpy arrays of item size 1, 2, 4 or 8 into one pack
-    frame on the GPU; copies through torch.  `kinds`: None (all "planes"), one
-    name or one per array.  The element widths are stored, dtypes and shapes
-    are not."""
+def _pack_host_tensors(arrays, what, device, optional=False):
+    """The arrays of a host pack call as flat integer device tensors (None stays None where `optional`)."""
     import torch
 
-    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
-                       nstates=nstates)
     tensors = []
     for m, data in enumerate(arrays):
+        if data is None and optional:
+            tensors.append(None)
+            continue
         a = np.ascontiguousarray(data)
         if a.dtype.itemsize not in _INT_VIEW:
-            raise ValueError(f"member {m}: item size {a.dtype.itemsize}: a pack takes 1, 2, 4 or 8 bytes")
-        tensors.append(torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(codec.device))
-    return codec.compress_pack(tensors, kinds).cpu().numpy().tobytes()
+            raise ValueError(f"{what} {m}: item size {a.dtype.itemsize}: a pack takes 1, 2, 4 or 8 bytes")
+        tensors.append(torch.from_numpy(a.reshape(-1).view(_INT_VIEW[a.dtype.itemsize]).copy()).to(device))
+    return tensors
 
 
-def pack_decompress(blob, dtypes, device=None) -> list:
-    """Decode a pack frame held in host memory into one 1-D numpy array per
-    member; `dtypes` is one dtype or one per member (each of the member's item
-    size); raises FseError on a frame-level error or with the first failed
-    block's status."""
+def pack_compress(arrays, kinds=None, block_size: int = 65536, table_log: int = 0, ckpt_interval: int = 128,
+                  nstates: int = 2, device=None, bases=None) -> bytes:
+    """Compress a list of numpy arrays of item size 1, 2, 4 or 8 into one pack
+    frame on the GPU; copies through torch.  `kinds`: None (all "planes"), one
+    name or one per array.  With `bases` (one entry per array: None or an
+    array of the same item size and count) the output is a versioned pack, as
+    BlockCodec.compress_pack.  The element widths are stored, dtypes and
+    shapes are not."""
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    tensors = _pack_host_tensors(arrays, "member", codec.device)
+    if bases is not None:
+        bases = _pack_host_tensors(bases, "base", codec.device, optional=True)
+    return codec.compress_pack(tensors, kinds, bases=bases).cpu().numpy().tobytes()
+
+
+def pack_decompress(blob, dtypes, device=None, bases=None) -> list:
+    """Decode a pack frame or a versioned pack held in host memory into one
+    1-D numpy array per member; `dtypes` is one dtype or one per member (each
+    of the member's item size); `bases`: one entry per member, None or the
+    array a diff member was coded against; raises FseError on a frame-level
+    error or with the first failed block's status."""
     import torch
 
     head = BlockCodec.pack_info(_buf(blob))  # not a pack: BAD_FRAME before any device work
@@ -2100,7 +2263,10 @@ def pack_decompress(blob, dtypes, device=None) -> list:
             raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, member {m} holds {head.elem_bytes[m]}-byte ones")
     codec = BlockCodec(device=device)
     buf = torch.from_numpy(_buf(blob).copy()).to(codec.device)
-    outs, status = codec.decompress_pack(buf, [getattr(torch, np.dtype(_INT_VIEW[w]).name) for w in head.elem_bytes])
+    if bases is not None:
+        bases = _pack_host_tensors(bases, "base", codec.device, optional=True)
+    outs, status = codec.decompress_pack(buf, [getattr(torch, np.dtype(_INT_VIEW[w]).name) for w in head.elem_bytes],
+                                         bases=bases)
     st = status.cpu().numpy()
     if st.any():
         b = int(np.flatnonzero(st)[0])
@@ -2140,7 +2306,7 @@ def estimate_choose(est):
 
 
 def container_kind(buf) -> str:
-    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed", "diff" or "pack" from
+    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed", "diff", "pack" or "vpack" from
     the magic of a container given as bytes, a numpy array or a tensor (its
     first 4 bytes come to the host); raises FseError (BAD_FRAME) for anything
     else."""
@@ -2152,6 +2318,8 @@ def container_kind(buf) -> str:
     k = load().fsehip_container_kind(_p(a), len(a))
     if k < 0:
         raise FseError(k, "fsehip_container_kind")
+    if k == KIND_VPACK:
+        return "vpack"
     return "sealed" if k == KIND_SEALED else "diff" if k == KIND_DIFF else "pack" if k == KIND_PACK else KINDS[k]
 
 
@@ -2185,7 +2353,7 @@ def auto_decompress(blob, dtype, device=None, base=None) -> np.ndarray:
         raise ValueError("a diff frame decodes against its base: pass base=")
     if kind in _ELEM:
         return _elem_decompress(kind, blob, dtype, device, base if kind == "diff" else None)
-    if kind == "pack":
+    if kind in ("pack", "vpack"):
         raise ValueError("a pack frame holds many tensors and goes to pack_decompress")
     if kind != "frame":
         raise ValueError("a sealed buffer goes to sealed_decompress")

@@ -1273,7 +1273,9 @@ typedef struct {
  *    pointer, len = bytes available; a sealed buffer reports
  *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's;
  *    a diff frame of section 2h FSEHIP_KIND_DIFF, which the estimate calls of
- *    section 2i take and those of this section refuse),
+ *    section 2i take and those of this section refuse; a pack frame of
+ *    section 2j FSEHIP_KIND_PACK and a versioned pack of section 2k
+ *    FSEHIP_KIND_VPACK),
  *    FSE_ERR_BAD_FRAME for len < 4 or any other magic, BAD_ARG for a null buf
  *    with len > 0.  Only the magic is read; the headers have their readers. */
 uint32_t fsehip_log2q8(uint32_t c);
@@ -1724,6 +1726,105 @@ int fsehip_pack_decompress_members(const fsehip_pack_info* info, const fsehip_pa
                                    uint64_t in_len, const uint32_t* sel, uint32_t n_sel, uint8_t* d_scratch,
                                    uint64_t scratch_cap, int32_t* d_member_status, int32_t* d_result,
                                    fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * (2k) Versioned pack: diff members against base tensors in a pack frame
+ *
+ * The next checkpoint against the previous one is every tensor of a
+ * state_dict against its predecessor: the diff frame of section 2h per
+ * tensor, the pack frame of section 2j for the list.  The versioned pack is
+ * both at once: a sibling of the pack frame with its own magic, over the same
+ * host code and the same tile kernels, whose member kind list gains the diff
+ * kind.  This is where the diff members that section 2j leaves out live.
+ *
+ * The layout is byte for byte that of section 2j (a 32-byte header, 16 bytes
+ * per member, one unchanged frame of section 2b over one image, planes
+ * plane-major from the top byte, every plane padded to 16) with
+ *    magic "FSEV", version = 1
+ *    kind  FSEHIP_KIND_PLANES, FSEHIP_KIND_DELTA or FSEHIP_KIND_DIFF
+ * For a diff member, z_m is the zigzag difference of section 2h of the
+ * member's elements against its base's, a tensor of the same width and count:
+ * z_i = zigzag(x_i - b_i) mod 2^(8 w), no restarts.  Planes and delta members
+ * are exactly as in 2j, so a versioned pack without a diff member differs
+ * from the pack frame of the same list in its magic only.
+ *
+ * THE CONTAINER DOES NOT IDENTIFY ITS BASES.  As with the diff frame, a
+ * decode against another base of the same size succeeds with every status
+ * FSE_OK and yields other values; which tensor a member was coded against is
+ * the caller's to know (a checkpoint step, a content hash beside the pack).
+ *
+ * The reader rules are those of 2j: BAD_FRAME for any nonzero reserved byte,
+ * another version, a kind outside {1, 2, 4} or a width outside the list,
+ * n_members above the cap, sums that overflow or differ from the two header
+ * fields, and an inner n_total other than image_bytes.  "FSEV" is BAD_FRAME to
+ * every other reader of this header (the frame, planes, delta, diff and check
+ * readers, fsehip_sealed_read_header, fsehip_pack_read_header and
+ * fsehip_pack_read_members) and their magics are BAD_FRAME here.
+ *
+ * Out of scope of version 1: sealing a versioned pack (section 2f), a
+ * per-member automatic kind (section 2i), element ranges inside a member.
+ *
+ * A failed inner block costs the elements with a byte in it, and for a delta
+ * member the rest of that restart group as well; for a diff member decoded in
+ * place the base's values there are lost too.  BAD_FRAME stores nothing to
+ * any member.
+ * ------------------------------------------------------------------------ */
+#define FSEHIP_KIND_VPACK 6u /* section 2k, magic "FSEV": fsehip_container_kind only */
+
+/* The calls mirror fsehip_pack_* one for one over the same fsehip_pack_member
+ * list (kind may be FSEHIP_KIND_DIFF) and fsehip_pack_info.  The host calls
+ * are those of section 2j for this container's magic and kinds;
+ * fsehip_vpack_scratch_bytes and fsehip_vpack_members_scratch_bytes also hold
+ * one base pointer per member. */
+uint64_t fsehip_vpack_image_bytes(const fsehip_pack_member* members, uint32_t n_members);
+uint64_t fsehip_vpack_bound(const fsehip_pack_member* members, uint32_t n_members, uint32_t block_size);
+uint64_t fsehip_vpack_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members);
+uint64_t fsehip_vpack_members_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, const uint32_t* sel,
+                                            uint32_t n_sel);
+uint64_t fsehip_vpack_plane_offset(const fsehip_pack_member* members, uint32_t n_members, uint32_t m, uint32_t k);
+int fsehip_vpack_read_header(const uint8_t* buf, size_t len, fsehip_pack_info* out);
+int fsehip_vpack_read_members(const uint8_t* buf, size_t len, fsehip_pack_member* members, uint32_t members_cap,
+                              fsehip_pack_info* out, fsehip_frame_info* inner);
+int fsehip_vpack_write_header(const fsehip_pack_member* members, uint32_t n_members, uint8_t* out);
+
+/* The device calls are those of section 2j with `d_bases` behind the member
+ * list: a HOST array of n_members device pointers, d_bases[m] the base of
+ * member m (n_elems elements of elem_bytes, aligned to elem_bytes).  An entry
+ * is ignored for planes and delta members and for members without elements;
+ * the array may be NULL when no member with elements is a diff member.
+ * fsehip_vpack_decompress_members needs the bases of the selected diff
+ * members only.  The pointers travel to the device with the descriptors and
+ * the head in the one copy through the stream's pinned staging: every call is
+ * asynchronous on `stream`, no host synchronisation.
+ *
+ * Reads: up to roundup(n_elems * elem_bytes, 4) bytes of a source and of a
+ * base, as fsehip_diff_*.  Stores: exactly n_elems * elem_bytes bytes per
+ * member, at element alignment.
+ *
+ * Before any device use, the checks of the fsehip_pack_* call, and: a diff
+ * member with elements whose base is NULL or not aligned to its elements is
+ * BAD_ARG.  On the decode side (merge, decompress, decompress_members) a diff
+ * member's destination may be its base itself (d_ptr == d_bases[m]: the
+ * in-place update of a checkpoint); any other overlap of a destination with
+ * another destination or with the base of a decoded diff member, counting
+ * only members with elements, is BAD_ARG.  On the split side bases and
+ * sources are only read and may overlap. */
+int fsehip_vpack_split(const fsehip_pack_member* members, uint32_t n_members, const void* const* d_bases,
+                       uint8_t* d_image, uint8_t* d_scratch, uint64_t scratch_cap, fsehip_stream_t stream);
+int fsehip_vpack_merge(const fsehip_pack_member* members, uint32_t n_members, const void* const* d_bases,
+                       const uint8_t* d_image, uint8_t* d_scratch, uint64_t scratch_cap, fsehip_stream_t stream);
+int fsehip_vpack_compress(const fsehip_frame_params* p, const fsehip_pack_member* members, uint32_t n_members,
+                          const void* const* d_bases, uint8_t* d_scratch, uint64_t scratch_cap, uint8_t* d_out,
+                          uint64_t out_cap, uint64_t* d_out_len, int32_t* d_result, fsehip_stream_t stream);
+int fsehip_vpack_decompress(const fsehip_pack_info* info, const fsehip_pack_member* members,
+                            const void* const* d_bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                            const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap,
+                            int32_t* d_block_status, int32_t* d_result, fsehip_stream_t stream);
+int fsehip_vpack_decompress_members(const fsehip_pack_info* info, const fsehip_pack_member* members,
+                                    const void* const* d_bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                                    const uint8_t* d_in, uint64_t in_len, const uint32_t* sel, uint32_t n_sel,
+                                    uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_member_status,
+                                    int32_t* d_result, fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
