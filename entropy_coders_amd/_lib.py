@@ -73,6 +73,10 @@ EXPORTS = (
     "fsehip_vpack_members_scratch_bytes", "fsehip_vpack_plane_offset", "fsehip_vpack_read_header",
     "fsehip_vpack_read_members", "fsehip_vpack_write_header", "fsehip_vpack_split", "fsehip_vpack_merge",
     "fsehip_vpack_compress", "fsehip_vpack_decompress", "fsehip_vpack_decompress_members",
+    "fsehip_mcheck_bytes", "fsehip_mcheck_read_header", "fsehip_mcheck_write_header", "fsehip_spack_read_header",
+    "fsehip_mcheck_scratch_bytes", "fsehip_spack_bound", "fsehip_spack_scratch_bytes",
+    "fsehip_spack_members_scratch_bytes", "fsehip_mcheck_build", "fsehip_mcheck_verify", "fsehip_spack_compress",
+    "fsehip_spack_decompress", "fsehip_spack_decompress_members",
 )
 
 STATUS = {
@@ -157,6 +161,8 @@ KIND_SEALED = 3                        # FSEHIP_KIND_SEALED: fsehip_container_ki
 KIND_DIFF = 4                          # FSEHIP_KIND_DIFF: of an "FSEB" buffer; fsehip_estimate_base's fifth entry
 KIND_PACK = 5                          # FSEHIP_KIND_PACK: of an "FSEM" buffer
 KIND_VPACK = 6                         # FSEHIP_KIND_VPACK: of an "FSEV" buffer
+KIND_SPACK = 7                         # FSEHIP_KIND_SPACK: of an "FSES" buffer
+MCHECK_BASES = 1                       # FSEHIP_MCHECK_BASES: the member check record's flag bit 0
 PACK_MAX_MEMBERS = 1 << 20             # FSEHIP_PACK_MAX_MEMBERS
 EST_NONE = (1 << 64) - 1               # FSEHIP_EST_NONE
 EST_RAW, EST_RLE, EST_FSE = 0, 1, 2    # FSEHIP_EST_*: the frame directory's block types
@@ -171,6 +177,12 @@ class PackInfo(C.Structure):
     """fsehip_pack_info: a pack frame's header fields; the member table follows at byte 32."""
     _fields_ = [("version", C.c_uint32), ("n_members", C.c_uint32), ("image_bytes", C.c_uint64),
                 ("content_bytes", C.c_uint64)]
+
+
+class McheckInfo(C.Structure):
+    """fsehip_mcheck_info: a member check record's header fields; the table (8 bytes per member) follows at byte 32."""
+    _fields_ = [("version", C.c_uint32), ("algorithm", C.c_uint32), ("flags", C.c_uint32), ("n_members", C.c_uint32),
+                ("content_bytes", C.c_uint64), ("header_crc", C.c_uint32), ("reserved", C.c_uint32)]
 
 
 class BlockEstimate(C.Structure):
@@ -384,6 +396,25 @@ def load() -> C.CDLL:
     lib.fsehip_vpack_compress.argtypes = [C.POINTER(FrameParams), PM, u32, BP, P, u64, P, u64, P, P, P]
     lib.fsehip_vpack_decompress.argtypes = [PKI, PM, BP, FI, u32, P, u64, P, u64, P, P, P]
     lib.fsehip_vpack_decompress_members.argtypes = [PKI, PM, BP, FI, u32, P, u64, C.POINTER(u32), u32, P, u64, P, P, P]
+    # the member check record and the sealed pack
+    MI, pu32_, pu64_ = C.POINTER(McheckInfo), C.POINTER(u32), C.POINTER(u64)
+    for name in ("fsehip_mcheck_bytes", "fsehip_mcheck_scratch_bytes", "fsehip_spack_bound",
+                 "fsehip_spack_scratch_bytes", "fsehip_spack_members_scratch_bytes"):
+        getattr(lib, name).restype = u64
+    lib.fsehip_mcheck_bytes.argtypes = [u32]
+    lib.fsehip_mcheck_read_header.argtypes = [P, sz, MI]
+    lib.fsehip_mcheck_write_header.argtypes = [MI, P]
+    lib.fsehip_spack_read_header.argtypes = [P, sz, MI, pu32_, pu64_]
+    lib.fsehip_mcheck_scratch_bytes.argtypes = [PM, u32, pu32_, u32, u32]
+    lib.fsehip_spack_bound.argtypes = [PM, u32, u32, u32]
+    lib.fsehip_spack_scratch_bytes.argtypes = [PM, u32, u32]
+    lib.fsehip_spack_members_scratch_bytes.argtypes = [PM, u32, u32, pu32_, u32]
+    lib.fsehip_mcheck_build.argtypes = [PM, BP, u32, P, P, u64, P]
+    lib.fsehip_mcheck_verify.argtypes = [MI, P, PM, pu32_, u32, u32, BP, P, u64, P, P, P]
+    lib.fsehip_spack_compress.argtypes = [C.POINTER(FrameParams), PM, u32, BP, u32, P, u64, P, u64, P, P, P]
+    lib.fsehip_spack_decompress.argtypes = [MI, PKI, u32, PM, BP, FI, u32, P, u64, P, u64, P, P, P, P, P, P]
+    lib.fsehip_spack_decompress_members.argtypes = [MI, PKI, u32, PM, BP, FI, u32, P, u64, pu32_, u32, P, u64, P, P,
+                                                    P, P, P, P]
     lib.fsehip_rank_fallbacks.argtypes = [C.c_int, C.POINTER(u32 * 3), C.c_int]
     lib.norm_histogram_try_from.argtypes = [P, C.POINTER(NormHistogram)]
     lib.fsehip_shared_table_bytes.argtypes = []

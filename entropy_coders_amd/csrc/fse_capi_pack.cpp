@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "fse_capi_common.h"
+#include "fse_mcheck_host.h"
 #include "fse_pack_host.h"
 
 using namespace fsehip::capi;
@@ -85,6 +86,19 @@ int launch_merge(PackFlavour f, const uint8_t* d_descs, uint32_t n, uint64_t til
     if (f == kFlavourVpack)
         return fsehip::launch_vpack_merge(descs_at(d_descs), bases_at(d_descs, n), n, tiles, planes, result, stream);
     return fsehip::launch_pack_merge(descs_at(d_descs), n, tiles, planes, result, stream);
+}
+
+// The sealed pack's decode (fse_capi_spack.cpp) brings a gate word that its
+// base verification has filled: the frame status joins it on the device, and
+// the merge is handed the gate in place of d_result, storing nothing when
+// either says BAD_FRAME.  A gate launch that fails ends the call: the merge is
+// never launched without the word it was to look at.  gate nullptr (the pack
+// calls themselves): the merge looks at d_result.
+int gated_merge(PackFlavour f, const uint8_t* d_descs, uint32_t n, uint64_t tiles, const uint8_t* planes,
+                const int32_t* d_result, int32_t* gate, void* stream) {
+    if (!gate) return launch_merge(f, d_descs, n, tiles, planes, d_result, stream);
+    if (const int rc = fsehip::launch_mcheck_gate(d_result, gate, stream)) return rc;
+    return launch_merge(f, d_descs, n, tiles, planes, gate, stream);
 }
 
 // the checks of a bare transform; *image = the image's bytes
@@ -170,10 +184,12 @@ int compress(PackFlavour f, const fsehip_frame_params* p, const fsehip_pack_memb
     return fsehip::launch_pack_finish(head_at(f, d_descs, n_members), head, d_out, d_out_len, stream);
 }
 
-int decompress(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
-               const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in,
-               uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_block_status, int32_t* d_result,
-               void* stream) {
+// The whole decode in two halves, so that the sealed pack can run the first,
+// verify its bases, and then run the second: every check before any device
+// use but the question for a device itself, then the launches.
+int decompress_check(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                     const void* const* bases, const fsehip_frame_info* inner, const uint8_t* d_in, uint64_t in_len,
+                     const uint8_t* d_scratch, uint64_t scratch_cap, const int32_t* d_result) {
     if (const int rc = decode_args(f, info, members, inner, d_in, in_len, d_result)) return rc;
     const uint32_t n = info->n_members;
     if (!d_scratch || !aligned(d_scratch, 16)) return FSE_ERR_BAD_ARG;
@@ -181,7 +197,14 @@ int decompress(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_me
     if (!fsehip::pack_decode_spans_ok(members, bases, nullptr, n)) return FSE_ERR_BAD_ARG;
     const uint64_t need = fsehip::pack_scratch_bytes(f, members, n);
     if (!need || scratch_cap < need) return FSE_ERR_DST_TOO_SMALL;
-    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    return FSE_OK;
+}
+
+int decompress_launch(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                      const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                      const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, int32_t* d_block_status,
+                      int32_t* d_result, int32_t* gate, void* stream) {
+    const uint32_t n = info->n_members;
     std::vector<PackDesc> descs(n);
     const uint64_t tiles = fsehip::pack_plan(members, n, descs.data());
     const uint64_t head = fsehip::pack_head_bytes(n), image = info->image_bytes;
@@ -193,36 +216,54 @@ int decompress(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_me
     if (const int rc = fsehip::launch_pack_check(head_at(f, d_descs, n), head, d_in, d_result, d_block_status,
                                                  inner->n_blocks, false, stream))
         return rc;
-    return launch_merge(f, d_descs, n, tiles, d_scratch, d_result, stream);
+    return gated_merge(f, d_descs, n, tiles, d_scratch, d_result, gate, stream);
 }
 
-// Scratch: the selected members' planes, stride_m bytes each, from offset 0 on
-// (every one 16-byte aligned); the plane ranges' statuses of the frame call;
-// the selected members' descriptors (and base pointers); the head bytes.
-int decompress_members(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
-                       const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
-                       const uint8_t* d_in, uint64_t in_len, const uint32_t* sel, uint32_t n_sel, uint8_t* d_scratch,
-                       uint64_t scratch_cap, int32_t* d_member_status, int32_t* d_result, void* stream) {
+int decompress(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+               const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in,
+               uint64_t in_len, uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_block_status, int32_t* d_result,
+               void* stream) {
+    if (const int rc = decompress_check(f, info, members, bases, inner, d_in, in_len, d_scratch, scratch_cap, d_result))
+        return rc;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    return decompress_launch(f, info, members, bases, inner, chunk_blocks, d_in, in_len, d_scratch, d_block_status,
+                             d_result, nullptr, stream);
+}
+
+// The selected-member decode, in the same two halves; the check half leaves
+// its plan for the launch half.  Scratch: the selected members' planes,
+// stride_m bytes each, from offset 0 on (every one 16-byte aligned); the plane
+// ranges' statuses of the frame call; the selected members' descriptors (and
+// base pointers); the head bytes.
+int members_check(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                  const void* const* bases, const fsehip_frame_info* inner, const uint8_t* d_in, uint64_t in_len,
+                  const uint32_t* sel, uint32_t n_sel, const uint8_t* d_scratch, uint64_t scratch_cap,
+                  const int32_t* d_result, fsehip::PackMembersPlan* plan) {
     if (const int rc = decode_args(f, info, members, inner, d_in, in_len, d_result)) return rc;
     const uint32_t n = info->n_members;
     if (!d_scratch || !aligned(d_scratch, 16) || (n_sel && !sel)) return FSE_ERR_BAD_ARG;
-    std::vector<PackDesc> descs;
-    std::vector<fsehip_frame_range> ranges;
-    uint64_t planes_bytes, tiles;
-    if (const int rc = fsehip::pack_plan_selected(members, n, sel, n_sel, &descs, &ranges, &planes_bytes, &tiles))
+    if (const int rc = fsehip::pack_plan_selected(members, n, sel, n_sel, &plan->descs, &plan->ranges,
+                                                  &plan->planes_bytes, &plan->tiles))
         return rc;
     if (!pointers_ok(members, bases, sel, n_sel)) return FSE_ERR_BAD_ARG;
     if (!fsehip::pack_decode_spans_ok(members, bases, sel, n_sel)) return FSE_ERR_BAD_ARG;
     const uint64_t need = fsehip::pack_members_scratch_bytes(f, members, n, sel, n_sel);
     if (!need || scratch_cap < need) return FSE_ERR_DST_TOO_SMALL;
-    if (!device_ok()) return FSE_ERR_NO_DEVICE;
-    const uint64_t head = fsehip::pack_head_bytes(n);
-    const uint32_t n_ranges = (uint32_t)ranges.size();
+    return FSE_OK;
+}
+
+int members_launch(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                   const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in,
+                   uint64_t in_len, const uint32_t* sel, uint32_t n_sel, const fsehip::PackMembersPlan& plan,
+                   uint8_t* d_scratch, int32_t* d_member_status, int32_t* d_result, int32_t* gate, void* stream) {
+    const uint32_t n = info->n_members;
+    const uint64_t head = fsehip::pack_head_bytes(n), planes_bytes = plan.planes_bytes;
+    const uint32_t n_ranges = (uint32_t)plan.ranges.size();
     int32_t* plane_status = reinterpret_cast<int32_t*>(d_scratch + planes_bytes);
     uint8_t* d_descs = d_scratch + planes_bytes + round_up(4ull * n_ranges, 16);
-    if (const int rc = upload(f, descs, members, n, bases, sel, d_descs, stream)) return rc;
-    if (const int rc = fsehip_frame_decompress_ranges(inner, chunk_blocks, d_in + head, in_len - head, ranges.data(),
-                                                      n_ranges, d_scratch, planes_bytes,
+    if (const int rc = upload(f, plan.descs, members, n, bases, sel, d_descs, stream)) return rc;
+    if (const int rc = fsehip_frame_decompress_ranges(inner, chunk_blocks, d_in + head, in_len - head,
+                                                      plan.ranges.data(), n_ranges, d_scratch, planes_bytes,
                                                       n_ranges ? plane_status : nullptr, d_result, stream))
         return rc;
     if (const int rc = fsehip::launch_pack_check(head_at(f, d_descs, n_sel), head, d_in, d_result, nullptr, 0, true,
@@ -231,10 +272,66 @@ int decompress_members(PackFlavour f, const fsehip_pack_info* info, const fsehip
     if (const int rc = fsehip::launch_pack_member_status(descs_at(d_descs), n_sel, plane_status, d_member_status,
                                                          d_result, stream))
         return rc;
-    return launch_merge(f, d_descs, n_sel, tiles, d_scratch, d_result, stream);
+    return gated_merge(f, d_descs, n_sel, plan.tiles, d_scratch, d_result, gate, stream);
+}
+
+int decompress_members(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                       const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                       const uint8_t* d_in, uint64_t in_len, const uint32_t* sel, uint32_t n_sel, uint8_t* d_scratch,
+                       uint64_t scratch_cap, int32_t* d_member_status, int32_t* d_result, void* stream) {
+    fsehip::PackMembersPlan plan;
+    if (const int rc = members_check(f, info, members, bases, inner, d_in, in_len, sel, n_sel, d_scratch, scratch_cap,
+                                     d_result, &plan))
+        return rc;
+    if (!device_ok()) return FSE_ERR_NO_DEVICE;
+    return members_launch(f, info, members, bases, inner, chunk_blocks, d_in, in_len, sel, n_sel, plan, d_scratch,
+                          d_member_status, d_result, nullptr, stream);
 }
 
 }  // namespace
+
+// the sealed pack's way in (fse_mcheck_host.h)
+namespace fsehip {
+
+int pack_compress_impl(PackFlavour f, const fsehip_frame_params* p, const fsehip_pack_member* members,
+                       uint32_t n_members, const void* const* bases, uint8_t* d_scratch, uint64_t scratch_cap,
+                       uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_len, int32_t* d_result, void* stream) {
+    return compress(f, p, members, n_members, bases, d_scratch, scratch_cap, d_out, out_cap, d_out_len, d_result,
+                    stream);
+}
+
+int pack_decompress_check(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                          const void* const* bases, const fsehip_frame_info* inner, const uint8_t* d_in,
+                          uint64_t in_len, const uint8_t* d_scratch, uint64_t scratch_cap, const int32_t* d_result) {
+    return decompress_check(f, info, members, bases, inner, d_in, in_len, d_scratch, scratch_cap, d_result);
+}
+
+int pack_decompress_launch(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                           const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                           const uint8_t* d_in, uint64_t in_len, uint8_t* d_scratch, int32_t* d_block_status,
+                           int32_t* d_result, int32_t* gate, void* stream) {
+    return decompress_launch(f, info, members, bases, inner, chunk_blocks, d_in, in_len, d_scratch, d_block_status,
+                             d_result, gate, stream);
+}
+
+int pack_members_check(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                       const void* const* bases, const fsehip_frame_info* inner, const uint8_t* d_in, uint64_t in_len,
+                       const uint32_t* sel, uint32_t n_sel, const uint8_t* d_scratch, uint64_t scratch_cap,
+                       const int32_t* d_result, PackMembersPlan* plan) {
+    return members_check(f, info, members, bases, inner, d_in, in_len, sel, n_sel, d_scratch, scratch_cap, d_result,
+                         plan);
+}
+
+int pack_members_launch(PackFlavour f, const fsehip_pack_info* info, const fsehip_pack_member* members,
+                        const void* const* bases, const fsehip_frame_info* inner, uint32_t chunk_blocks,
+                        const uint8_t* d_in, uint64_t in_len, const uint32_t* sel, uint32_t n_sel,
+                        const PackMembersPlan& plan, uint8_t* d_scratch, int32_t* d_member_status, int32_t* d_result,
+                        int32_t* gate, void* stream) {
+    return members_launch(f, info, members, bases, inner, chunk_blocks, d_in, in_len, sel, n_sel, plan, d_scratch,
+                          d_member_status, d_result, gate, stream);
+}
+
+}  // namespace fsehip
 
 extern "C" {
 

@@ -199,16 +199,6 @@ int check_ranges_ok(const fsehip_check_info* info, uint64_t out_cap, const fsehi
     return FSE_OK;
 }
 
-namespace {
-// 0xFFFFFFFF * x^(8 a): a = the bytes of a block of `len` bytes that starts
-// `alpha` bytes into a 16-byte word and lie ahead of its last word
-uint32_t init_share(uint32_t alpha, uint64_t len) {
-    if (!len) return 0xFFFFFFFFu;
-    const uint64_t last_word = (alpha + len - 1u) >> 4;
-    return crc::mulmod(0xFFFFFFFFu, crc::xpow8(last_word ? 16u * last_word - alpha : 0u));
-}
-}  // namespace
-
 void check_span(CheckSpans* S, uint32_t i, const void* data, uint64_t off, uint64_t b0, uint64_t nb,
                 uint64_t n_content, uint32_t check_log) {
     const uint64_t B = 1ull << check_log;
@@ -217,8 +207,8 @@ void check_span(CheckSpans* S, uint32_t i, const void* data, uint64_t off, uint6
     S->off[i] = off;
     S->b0[i] = (uint32_t)b0;
     S->nb[i] = (uint32_t)nb;
-    S->k_full[i] = init_share(alpha, B);
-    S->k_last[i] = init_share(alpha, tail ? tail : B);
+    S->k_full[i] = crc::init_share(alpha, B);
+    S->k_last[i] = crc::init_share(alpha, tail ? tail : B);
 }
 
 CombinePlan check_combine_plan(uint64_t n_content, uint32_t check_log, uint32_t n_cb) {

@@ -87,6 +87,15 @@ constexpr Weights make_weights() {
     return W;
 }
 
+// 0xFFFFFFFF * x^(8 a): a = the bytes of a block of `len` bytes that starts
+// `alpha` bytes into a 16-byte word and lie ahead of its last word -- the init
+// value's share of the block's CRC
+inline uint32_t init_share(uint32_t alpha, uint64_t len) {
+    if (!len) return 0xFFFFFFFFu;
+    const uint64_t last_word = (alpha + len - 1u) >> 4;
+    return mulmod(0xFFFFFFFFu, xpow8(last_word ? 16u * last_word - alpha : 0u));
+}
+
 }  // namespace crc
 
 constexpr uint32_t kCheckHeaderBytes = 32;

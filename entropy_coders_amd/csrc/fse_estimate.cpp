@@ -88,6 +88,7 @@ int fsehip_container_kind(const uint8_t* buf, size_t len) {
         case 'B': return (int)FSEHIP_KIND_DIFF;
         case 'M': return (int)FSEHIP_KIND_PACK;
         case 'V': return (int)FSEHIP_KIND_VPACK;
+        case 'S': return (int)FSEHIP_KIND_SPACK;
         default: return FSE_ERR_BAD_FRAME;
     }
 }

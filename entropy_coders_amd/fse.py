@@ -11,7 +11,8 @@ import threading
 
 import numpy as np
 
-from ._lib import (EST_NONE, KIND_DIFF, KIND_PACK, KIND_SEALED, KIND_VPACK, KINDS, SEALED_KINDS, BitStackReaderState,
+from ._lib import (EST_NONE, KIND_DIFF, KIND_PACK, KIND_SEALED, KIND_SPACK, KIND_VPACK, KINDS, MCHECK_BASES, SEALED_KINDS,
+                   BitStackReaderState, McheckInfo,
                    BitStackWriterState, BitStreamReaderState, CheckInfo, DecodeTable, DeltaInfo, DiffInfo, EncodeTable,
                    FrameInfo, FrameParams, FrameRange, FseError, Histogram, NormHistogram, PackInfo, PackMember, Params,
                    PlanesInfo, PlanesRange, check, load)
@@ -2066,6 +2067,203 @@ class BlockCodec:
         check(int(result[0].item()), "pack frame")
         return outs, status
 
+    # ------------------------------------------------------------ the sealed pack
+    # (fsehip.h section 2l.)  The member check record -- one CRC-32 per
+    # member's content and, for diff members, per base -- in front of an
+    # unchanged pack frame or versioned pack.  On decode the bases are verified
+    # before the merge may store a byte (one wrong base: nothing is stored, in
+    # place or not), the destinations after it.
+    def pack_sealed_bound(self, members, n: int, versioned: bool = False) -> int:
+        return int(self.lib.fsehip_spack_bound(members, n, int(versioned), self.block_size))
+
+    def pack_sealed_scratch_bytes(self, members, n: int, versioned: bool = False) -> int:
+        return int(self.lib.fsehip_spack_scratch_bytes(members, n, int(versioned)))
+
+    def pack_sealed_members_scratch_bytes(self, members, n: int, indices, versioned: bool = False) -> int:
+        sel = (C.c_uint32 * max(len(indices), 1))(*indices)
+        return int(self.lib.fsehip_spack_members_scratch_bytes(members, n, int(versioned), sel, len(indices)))
+
+    def mcheck_scratch_bytes(self, members, n: int, indices=None, with_bases: bool = False) -> int:
+        sel = None if indices is None else (C.c_uint32 * max(len(indices), 1))(*indices)
+        return int(self.lib.fsehip_mcheck_scratch_bytes(members, n, sel, 0 if indices is None else len(indices),
+                                                        int(with_bases)))
+
+    def mcheck_build(self, tensors, bases=None, kinds=None):
+        """The member check record of a list of contiguous device tensors as
+        they lie (fsehip_mcheck_build): a uint8 device tensor of 32 + 8 n
+        bytes.  With `bases` (as compress_pack) the diff members' base CRCs
+        are recorded.  No synchronisation."""
+        t = self.torch
+        n, versioned, barr = len(tensors), bases is not None, None
+        if versioned:
+            kinds, barr = self.pack_bases(tensors, bases, kinds)
+        members = self.pack_members(tensors, kinds, versioned)
+        need = self.mcheck_scratch_bytes(members, n, None, versioned)
+        if not need:
+            raise FseError(-14, "fsehip_mcheck_scratch_bytes")
+        scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        record = t.empty(32 + 8 * n, dtype=t.uint8, device=self.device)
+        check(self.lib.fsehip_mcheck_build(members, barr, n, C.c_void_p(record.data_ptr()),
+                                           C.c_void_p(scratch.data_ptr()), scratch.numel(), self._stream()),
+              "fsehip_mcheck_build")
+        return record
+
+    def compress_pack_sealed_into(self, members, n: int, scratch, out, out_len, result, chunk_blocks: int = 0,
+                                  bases=None, check_bases: bool = True) -> None:
+        """fsehip_spack_compress, no synchronisation: as compress_pack_into
+        with `scratch` >= pack_sealed_scratch_bytes and `out` >=
+        pack_sealed_bound; `bases` (pack_bases' pointer array) makes the inner
+        container a versioned pack."""
+        p = self._frame_params(chunk_blocks)
+        check(self.lib.fsehip_spack_compress(C.byref(p), members, n, bases, int(bool(check_bases)),
+                                             C.c_void_p(scratch.data_ptr()), scratch.numel(),
+                                             C.c_void_p(out.data_ptr()), out.numel(), C.c_void_p(out_len.data_ptr()),
+                                             C.c_void_p(result.data_ptr()), self._stream()), "fsehip_spack_compress")
+
+    def compress_pack_sealed(self, tensors, kinds=None, bases=None, check_bases: bool = True, chunk_blocks: int = 0):
+        """compress_pack with the member check record in front: a sealed pack,
+        a uint8 device tensor of its exact length.  With `bases` the inner
+        container is a versioned pack, and with `check_bases` the record also
+        holds every diff member's base CRC, so that a decode against another
+        base is refused before it stores a byte.  One synchronisation, to read
+        the length."""
+        t = self.torch
+        n, versioned, barr = len(tensors), bases is not None, None
+        if versioned:
+            kinds, barr = self.pack_bases(tensors, bases, kinds)
+        members = self.pack_members(tensors, kinds, versioned)
+        bound = self.pack_sealed_bound(members, n, versioned)
+        need = self.pack_sealed_scratch_bytes(members, n, versioned)
+        if not bound or not need:
+            raise FseError(-14, "fsehip_spack_bound")
+        scratch = t.empty(need, dtype=t.uint8, device=self.device)
+        out = t.empty(bound, dtype=t.uint8, device=self.device)
+        out_len = t.zeros(1, dtype=t.int64, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        self.compress_pack_sealed_into(members, n, scratch, out, out_len, result, chunk_blocks, barr, check_bases)
+        return out[: int(out_len.item())]
+
+    @staticmethod
+    def pack_sealed_info(buf):
+        """The head of a sealed pack given as bytes, a numpy array or a tensor:
+        (record, head) with `record` the McheckInfo of the member check record
+        (`record.flags & 1`: base CRCs recorded) and `head` the PackHead of the
+        pack behind it, which starts at byte 32 + 8 n; raises FseError
+        (BAD_FRAME) otherwise."""
+        def take(lo, hi):
+            if hasattr(buf, "data_ptr"):  # a torch tensor
+                return buf[lo:hi].cpu().numpy().tobytes()
+            return bytes(memoryview(buf)[lo:hi])
+
+        lib = load()
+        a = np.frombuffer(take(0, 32), dtype=np.uint8)
+        rec = McheckInfo()
+        check(lib.fsehip_mcheck_read_header(_p(a), len(a), C.byref(rec)), "fsehip_mcheck_read_header")
+        off = 32 + 8 * rec.n_members
+        a = np.frombuffer(take(0, off + 32), dtype=np.uint8)
+        versioned, inner_off = C.c_uint32(0), C.c_uint64(0)
+        check(lib.fsehip_spack_read_header(_p(a), len(a), C.byref(rec), C.byref(versioned), C.byref(inner_off)),
+              "fsehip_spack_read_header")
+        head = BlockCodec.pack_info(np.frombuffer(take(off, off + 32 + 16 * rec.n_members + 32), dtype=np.uint8))
+        if (head.container == "vpack") != bool(versioned.value):
+            raise FseError(-19, "sealed pack")
+        return rec, head
+
+    def _pack_sealed_call(self, buf, rec, head, indices, selected, outs, scratch, status, result, member_check,
+                          base_check, check_result, chunk_blocks, bases) -> None:
+        versioned = head.container == "vpack"
+        outs = self._pack_outs(head, indices, [o.dtype for o in outs], outs)
+        members = self._pack_point(head, indices, outs)
+        barr = self._pack_decode_bases(head, indices, bases) if versioned else None
+        ptr = lambda x: C.c_void_p(x.data_ptr()) if x is not None else None  # noqa: E731
+        if selected:
+            sel = (C.c_uint32 * max(len(indices), 1))(*indices)
+            check(self.lib.fsehip_spack_decompress_members(
+                C.byref(rec), C.byref(head.info), int(versioned), members, barr, C.byref(head.inner), chunk_blocks,
+                ptr(buf), buf.numel(), sel, len(indices), ptr(scratch), scratch.numel(), ptr(status), ptr(result),
+                ptr(member_check), ptr(base_check), ptr(check_result), self._stream()),
+                "fsehip_spack_decompress_members")
+        else:
+            check(self.lib.fsehip_spack_decompress(
+                C.byref(rec), C.byref(head.info), int(versioned), members, barr, C.byref(head.inner), chunk_blocks,
+                ptr(buf), buf.numel(), ptr(scratch), scratch.numel(), ptr(status), ptr(result), ptr(member_check),
+                ptr(base_check), ptr(check_result), self._stream()), "fsehip_spack_decompress")
+
+    def decompress_pack_sealed_into(self, buf, rec, head, outs, scratch, block_status, result, member_check,
+                                    base_check, check_result, chunk_blocks: int = 0, bases=None) -> None:
+        """fsehip_spack_decompress, no synchronisation: `rec`, `head` from
+        pack_sealed_info, `outs`, `block_status`, `result` and `bases` as
+        decompress_pack_into, `scratch` >= pack_sealed_scratch_bytes,
+        `member_check` / `base_check` one int32 per member or None,
+        `check_result` four int32."""
+        self._pack_sealed_call(buf, rec, head, list(range(head.info.n_members)), False, outs, scratch, block_status,
+                               result, member_check, base_check, check_result, chunk_blocks, bases)
+
+    def decompress_pack_members_sealed_into(self, buf, rec, head, indices, outs, scratch, member_status, result,
+                                            member_check, base_check, check_result, chunk_blocks: int = 0,
+                                            bases=None) -> None:
+        """fsehip_spack_decompress_members, no synchronisation: as
+        decompress_pack_members_into with `scratch` >=
+        pack_sealed_members_scratch_bytes and the check outputs of
+        decompress_pack_sealed_into, one entry per index."""
+        self._pack_sealed_call(buf, rec, head, [int(i) for i in indices], True, outs, scratch, member_status, result,
+                               member_check, base_check, check_result, chunk_blocks, bases)
+
+    def decompress_pack_sealed(self, buf, dtypes, bases=None, outs=None, chunk_blocks: int = 0,
+                               with_result: bool = False):
+        """Decode a sealed pack (a uint8 device tensor) as decompress_pack
+        does its pack.  The bases of the diff members are verified against the
+        record first: if one fails, nothing is stored to any member (with
+        outs=bases the old checkpoint is untouched).  Returns (tensors,
+        block_status, member_check, base_check): per member FSE_OK or
+        CHECKSUM (-21) for the content that lies at its destination after the
+        call, and for its base.  Raises FseError for a frame-level error
+        (BAD_FRAME) of the pack or of the record.  `with_result`: the four
+        int32 of fsehip_spack_decompress's d_check_result as a fifth item."""
+        t = self.torch
+        rec, head = self.pack_sealed_info(buf)
+        n, versioned = head.info.n_members, head.container == "vpack"
+        outs = self._pack_outs(head, list(range(n)), dtypes, outs)
+        scratch = t.empty(self.pack_sealed_scratch_bytes(head.members, n, versioned), dtype=t.uint8, device=self.device)
+        status = t.zeros(head.inner.n_blocks, dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        mcheck = t.zeros(n, dtype=t.int32, device=self.device)
+        bcheck = t.zeros(n, dtype=t.int32, device=self.device)
+        cres = t.zeros(4, dtype=t.int32, device=self.device)
+        self.decompress_pack_sealed_into(buf, rec, head, outs, scratch, status, result, mcheck, bcheck, cres,
+                                         chunk_blocks, bases)
+        check(int(result[0].item()), "pack frame")
+        if int(cres[0].item()) == -19:
+            raise FseError(-19, "member check record")
+        return (outs, status, mcheck, bcheck, cres) if with_result else (outs, status, mcheck, bcheck)
+
+    def decompress_pack_members_sealed(self, buf, indices, dtypes, bases=None, outs=None, chunk_blocks: int = 0,
+                                       with_result: bool = False):
+        """Decode only the members `indices` of a sealed pack, as
+        decompress_pack_members; whole members are verified, and the gate
+        looks at the selected members' bases.  Returns (tensors,
+        member_status, member_check, base_check), one entry per index."""
+        t = self.torch
+        rec, head = self.pack_sealed_info(buf)
+        indices = [int(i) for i in indices]
+        if len(set(indices)) != len(indices):
+            raise ValueError("a member is selected twice")
+        versioned = head.container == "vpack"
+        outs = self._pack_outs(head, indices, dtypes, outs)
+        need = self.pack_sealed_members_scratch_bytes(head.members, head.info.n_members, indices, versioned)
+        scratch = t.empty(max(need, 16), dtype=t.uint8, device=self.device)
+        status = t.zeros(len(indices), dtype=t.int32, device=self.device)
+        result = t.zeros(2, dtype=t.int32, device=self.device)
+        mcheck = t.zeros(len(indices), dtype=t.int32, device=self.device)
+        bcheck = t.zeros(len(indices), dtype=t.int32, device=self.device)
+        cres = t.zeros(4, dtype=t.int32, device=self.device)
+        self.decompress_pack_members_sealed_into(buf, rec, head, indices, outs, scratch, status, result, mcheck, bcheck,
+                                                 cres, chunk_blocks, bases)
+        check(int(result[0].item()), "pack frame")
+        if int(cres[0].item()) == -19:
+            raise FseError(-19, "member check record")
+        return (outs, status, mcheck, bcheck, cres) if with_result else (outs, status, mcheck, bcheck)
+
     def block_bytes(self, cb: dict, b: int) -> bytes:
         """Compressed bytes of block b (host copy) -- for parity checks."""
         ln = int(cb["comp_len"][b].item())
@@ -2274,6 +2472,60 @@ def pack_decompress(blob, dtypes, device=None, bases=None) -> list:
     return [o.cpu().numpy().view(dt) for o, dt in zip(outs, dts)]
 
 
+def pack_sealed_info(buf):
+    """`BlockCodec.pack_sealed_info`: the record and the head of a sealed pack (fsehip.h section 2l)."""
+    return BlockCodec.pack_sealed_info(buf)
+
+
+def pack_sealed_compress(arrays, kinds=None, bases=None, check_bases: bool = True, block_size: int = 65536,
+                         table_log: int = 0, ckpt_interval: int = 128, nstates: int = 2, device=None) -> bytes:
+    """pack_compress with the member check record in front (a sealed pack,
+    fsehip.h section 2l); with `bases` and `check_bases` the record holds the
+    diff members' base CRCs as well."""
+    codec = BlockCodec(block_size=block_size, table_log=table_log, ckpt_interval=ckpt_interval, device=device,
+                       nstates=nstates)
+    tensors = _pack_host_tensors(arrays, "member", codec.device)
+    if bases is not None:
+        bases = _pack_host_tensors(bases, "base", codec.device, optional=True)
+    return codec.compress_pack_sealed(tensors, kinds, bases=bases, check_bases=check_bases).cpu().numpy().tobytes()
+
+
+def pack_sealed_decompress(blob, dtypes, bases=None, device=None) -> list:
+    """Decode a sealed pack held in host memory as pack_decompress does a
+    pack, and verify it: raises FseError("CHECKSUM") naming the members whose
+    base does not match the record (nothing was decoded then) or, failing
+    that, the members whose content does not; BAD_FRAME for a damaged head;
+    the first failed block's status otherwise."""
+    import torch
+
+    rec, head = BlockCodec.pack_sealed_info(_buf(blob))  # not a sealed pack: BAD_FRAME before any device work
+    n = head.info.n_members
+    dts = [np.dtype(d) for d in (dtypes if isinstance(dtypes, (list, tuple)) else [dtypes] * n)]
+    if len(dts) != n:
+        raise ValueError(f"{len(dts)} dtypes for {n} members")
+    for m, dt in enumerate(dts):
+        if dt.itemsize != head.elem_bytes[m]:
+            raise ValueError(f"dtype {dt} has {dt.itemsize}-byte items, member {m} holds {head.elem_bytes[m]}-byte ones")
+    codec = BlockCodec(device=device)
+    buf = torch.from_numpy(_buf(blob).copy()).to(codec.device)
+    if bases is not None:
+        bases = _pack_host_tensors(bases, "base", codec.device, optional=True)
+    outs, status, mcheck, bcheck = codec.decompress_pack_sealed(
+        buf, [getattr(torch, np.dtype(_INT_VIEW[w]).name) for w in head.elem_bytes], bases=bases)
+    bad_base = np.flatnonzero(bcheck.cpu().numpy())
+    if bad_base.size:
+        raise FseError(-21, f"sealed pack: base of member(s) {bad_base.tolist()} differs from the recorded base; "
+                            "nothing was decoded")
+    st = status.cpu().numpy()
+    if st.any():
+        b = int(np.flatnonzero(st)[0])
+        raise FseError(int(st[b]), f"pack frame block {b}")
+    bad = np.flatnonzero(mcheck.cpu().numpy())
+    if bad.size:
+        raise FseError(-21, f"sealed pack: content of member(s) {bad.tolist()}")
+    return [o.cpu().numpy().view(dt) for o, dt in zip(outs, dts)]
+
+
 def log2q8(c: int) -> int:
     """`fsehip_log2q8`: the estimate's 256 * log2(c) for 1 <= c <= 32768 (host, no device)."""
     if not 1 <= c <= 32768:
@@ -2306,7 +2558,7 @@ def estimate_choose(est):
 
 
 def container_kind(buf) -> str:
-    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed", "diff", "pack" or "vpack" from
+    """`fsehip_container_kind`: "frame", "planes", "delta", "sealed", "diff", "pack", "vpack" or "spack" from
     the magic of a container given as bytes, a numpy array or a tensor (its
     first 4 bytes come to the host); raises FseError (BAD_FRAME) for anything
     else."""
@@ -2320,6 +2572,8 @@ def container_kind(buf) -> str:
         raise FseError(k, "fsehip_container_kind")
     if k == KIND_VPACK:
         return "vpack"
+    if k == KIND_SPACK:
+        return "spack"
     return "sealed" if k == KIND_SEALED else "diff" if k == KIND_DIFF else "pack" if k == KIND_PACK else KINDS[k]
 
 
@@ -2588,4 +2842,5 @@ __all__ = ["BITS_ADVANCE", "BITS_PEEK", "BITS_READ", "BitStackReader", "BitStack
            "diff_decompress",
            "sealed_compress", "sealed_decompress", "crc32", "crc32_combine", "CheckInfo",
            "auto_compress", "auto_decompress", "container_kind", "estimate_choose", "log2q8",
-           "pack_compress", "pack_decompress", "pack_info", "PackHead"]
+           "pack_compress", "pack_decompress", "pack_info", "PackHead",
+           "pack_sealed_compress", "pack_sealed_decompress", "pack_sealed_info", "McheckInfo", "MCHECK_BASES"]

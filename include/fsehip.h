@@ -1274,8 +1274,8 @@ typedef struct {
  *    FSEHIP_KIND_SEALED, its container's kind is fsehip_sealed_read_header's;
  *    a diff frame of section 2h FSEHIP_KIND_DIFF, which the estimate calls of
  *    section 2i take and those of this section refuse; a pack frame of
- *    section 2j FSEHIP_KIND_PACK and a versioned pack of section 2k
- *    FSEHIP_KIND_VPACK),
+ *    section 2j FSEHIP_KIND_PACK, a versioned pack of section 2k
+ *    FSEHIP_KIND_VPACK and a sealed pack of section 2l FSEHIP_KIND_SPACK),
  *    FSE_ERR_BAD_FRAME for len < 4 or any other magic, BAD_ARG for a null buf
  *    with len > 0.  Only the magic is read; the headers have their readers. */
 uint32_t fsehip_log2q8(uint32_t c);
@@ -1599,9 +1599,10 @@ int fsehip_estimate_choose_base(const uint64_t est[5]);
  * (fsehip_sealed_read_header included) and their magics are BAD_FRAME here.
  *
  * As the other element frames, the container stores neither names, dtypes,
- * shapes nor bases.  Diff members (section 2h), a per-member automatic kind
- * (section 2g) and sealing a pack (section 2f) are out of scope of version 1;
- * the kind byte and the reserved fields leave room for them.
+ * shapes nor bases.  Diff members (section 2h) live in the versioned pack of
+ * section 2k, and sealing a pack is the member check record of section 2l.
+ * A per-member automatic kind (section 2g) is out of scope of version 1; the
+ * kind byte and the reserved fields leave room for it.
  *
  * A failed inner block costs the elements with a byte in it, and for a delta
  * member the rest of that restart group as well; BAD_FRAME stores nothing to
@@ -1751,7 +1752,9 @@ int fsehip_pack_decompress_members(const fsehip_pack_info* info, const fsehip_pa
  * THE CONTAINER DOES NOT IDENTIFY ITS BASES.  As with the diff frame, a
  * decode against another base of the same size succeeds with every status
  * FSE_OK and yields other values; which tensor a member was coded against is
- * the caller's to know (a checkpoint step, a content hash beside the pack).
+ * the caller's to know (a checkpoint step, a content hash beside the pack) --
+ * or the sealed pack's of section 2l, whose record holds every base's CRC-32
+ * and whose decode verifies the bases before it stores a byte.
  *
  * The reader rules are those of 2j: BAD_FRAME for any nonzero reserved byte,
  * another version, a kind outside {1, 2, 4} or a width outside the list,
@@ -1761,8 +1764,9 @@ int fsehip_pack_decompress_members(const fsehip_pack_info* info, const fsehip_pa
  * readers, fsehip_sealed_read_header, fsehip_pack_read_header and
  * fsehip_pack_read_members) and their magics are BAD_FRAME here.
  *
- * Out of scope of version 1: sealing a versioned pack (section 2f), a
- * per-member automatic kind (section 2i), element ranges inside a member.
+ * A versioned pack is sealed by the member check record of section 2l.  Out
+ * of scope of version 1: a per-member automatic kind (section 2i), element
+ * ranges inside a member.
  *
  * A failed inner block costs the elements with a byte in it, and for a delta
  * member the rest of that restart group as well; for a diff member decoded in
@@ -1825,6 +1829,175 @@ int fsehip_vpack_decompress_members(const fsehip_pack_info* info, const fsehip_p
                                     const uint8_t* d_in, uint64_t in_len, const uint32_t* sel, uint32_t n_sel,
                                     uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_member_status,
                                     int32_t* d_result, fsehip_stream_t stream);
+
+/* ------------------------------------------------------------------------
+ * (2l) Sealed pack: per-member CRC-32 of contents and bases, verified on device
+ *
+ * The check record of section 2f covers one contiguous content, and a pack's
+ * members lie wherever the caller's tensors do; a versioned pack decoded
+ * against the wrong previous checkpoint returns wrong weights with every block
+ * status FSE_OK, and in place it has overwritten the old checkpoint by then.
+ * The member check record holds one CRC-32 per member's content and, for diff
+ * members, one per base; they are computed over all members in a constant
+ * number of launches, travel in front of an unchanged pack, and on decode the
+ * bases are verified BEFORE the merge may store a byte, the destinations
+ * after it.  This library's own record, version 1; integers little-endian, no
+ * padding, any byte address:
+ *
+ *   header, 32 bytes
+ *    0  u8[4] magic "FSES"
+ *    4  u8    version = 1
+ *    5  u8    algorithm = 1 (FSEHIP_CHECK_CRC32)
+ *    6  u8    flags: bit 0 (FSEHIP_MCHECK_BASES) = base CRCs recorded; other bits 0
+ *    7  u8    0
+ *    8  u32   n_members
+ *   12  u32   reserved = 0
+ *   16  u64   content_bytes   (= the pack's content_bytes)
+ *   24  u32   reserved = 0
+ *   28  u32   header_crc      CRC-32 of bytes 0..27
+ *   table, n_members x 8 bytes
+ *    0  u32   content_crc     CRC-32 (zlib's) of the member's n_elems * w bytes; 0 when empty
+ *    4  u32   base_crc        CRC-32 of the base's n_elems * w bytes for a diff member with
+ *                             elements when flag bit 0 is set; otherwise 0
+ *
+ * A sealed pack is this record followed directly by exactly one pack frame
+ * ("FSEM", section 2j) or versioned pack ("FSEV", section 2k), to the end of
+ * the buffer; the inner container's bytes are unchanged.  The record's
+ * n_members and content_bytes equal the pack's, and flag bit 0 is valid only
+ * in front of "FSEV"; a reader rejects (BAD_FRAME) anything else, any nonzero
+ * reserved byte, another version or algorithm and a wrong header_crc.  "FSES"
+ * is BAD_FRAME to every other reader and their magics are BAD_FRAME here.  The
+ * record's size, 32 + 8 n, is known before anything runs, so the pack is
+ * compressed straight to its final place.
+ *
+ * The table is deliberately not covered by a CRC of its own: a damaged entry
+ * shows as CHECKSUM of that member, or as a failed base -- both the safe
+ * direction.  Granularity is the member, the unit fsehip_pack_decompress_members
+ * reports, not section 2f's 64 KiB: a selected-member decode verifies whole
+ * members, with none of section 2f's partial-block caveat.
+ *
+ * The gate is all or nothing: one base that fails its CRC (or a record header
+ * on the device that differs from the caller's) and the merge stores nothing
+ * to any member, in place or not -- the right rule for a checkpoint update.
+ * ------------------------------------------------------------------------ */
+#define FSEHIP_KIND_SPACK 7u /* section 2l, magic "FSES": fsehip_container_kind only */
+#define FSEHIP_MCHECK_BASES 1u /* flags bit 0: the table's base CRCs are recorded */
+
+typedef struct fsehip_mcheck_info {
+    uint32_t version;
+    uint32_t algorithm; /* FSEHIP_CHECK_CRC32 */
+    uint32_t flags;     /* FSEHIP_MCHECK_BASES or 0 */
+    uint32_t n_members;
+    uint64_t content_bytes;
+    uint32_t header_crc;
+    uint32_t reserved; /* 0 */
+} fsehip_mcheck_info;
+
+/* Host functions, no device.
+ *  fsehip_mcheck_bytes: the record's size, 32 + 8 n; 0 above
+ *    FSEHIP_PACK_MAX_MEMBERS.
+ *  fsehip_mcheck_read_header: parses 32 bytes; BAD_FRAME and *out zeroed for
+ *    fewer bytes or a broken rule.  fsehip_mcheck_write_header: the 32 bytes of
+ *    valid fields (header_crc is computed, not read); BAD_ARG otherwise.
+ *  fsehip_spack_read_header: the record's header of a sealed pack, whether the
+ *    pack behind it is versioned, and where it starts (hand buf + *inner_off to
+ *    fsehip_pack_read_members or fsehip_vpack_read_members); BAD_FRAME with
+ *    every output zeroed for any rule above.
+ *  fsehip_mcheck_scratch_bytes: the scratch of fsehip_mcheck_build (sel NULL,
+ *    with_bases as d_bases is given) and of fsehip_mcheck_verify (the members
+ *    sel[0 .. n_sel), or all for sel NULL; with_bases 0); 0 for an invalid list
+ *    or selection.
+ *  fsehip_spack_bound, fsehip_spack_scratch_bytes,
+ *  fsehip_spack_members_scratch_bytes: as fsehip_pack_* / fsehip_vpack_*
+ *    (`versioned` says which) plus the record and the check kernels' scratch. */
+uint64_t fsehip_mcheck_bytes(uint32_t n_members);
+int fsehip_mcheck_read_header(const uint8_t* hdr, size_t len, fsehip_mcheck_info* out);
+int fsehip_mcheck_write_header(const fsehip_mcheck_info* info, uint8_t hdr[32]);
+int fsehip_spack_read_header(const uint8_t* buf, size_t len, fsehip_mcheck_info* info, uint32_t* versioned,
+                             uint64_t* inner_off);
+uint64_t fsehip_mcheck_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, const uint32_t* sel,
+                                     uint32_t n_sel, uint32_t with_bases);
+uint64_t fsehip_spack_bound(const fsehip_pack_member* members, uint32_t n_members, uint32_t versioned,
+                            uint32_t block_size);
+uint64_t fsehip_spack_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, uint32_t versioned);
+uint64_t fsehip_spack_members_scratch_bytes(const fsehip_pack_member* members, uint32_t n_members, uint32_t versioned,
+                                            const uint32_t* sel, uint32_t n_sel);
+
+/* The record of the members as they lie, to d_record (any address,
+ * fsehip_mcheck_bytes): content CRCs of every member at its d_ptr and, with
+ * d_bases (a HOST array of device pointers as in section 2k; NULL: none, flag
+ * bit 0 clear), the base CRCs of the diff members.  Three launches whatever n:
+ * one CRC per 64 KiB work unit of every span, the units combined per span, the
+ * table and header written.  d_scratch: 16-byte aligned,
+ * fsehip_mcheck_scratch_bytes.  Members are read at element alignment: whole
+ * aligned 16-byte words that hold a content byte, never more.  Asynchronous on
+ * `stream`, no host synchronisation.  Before any device use: BAD_ARG (a null
+ * pointer, a member or base null or misaligned with elements), UNSUPPORTED (an
+ * invalid list), DST_TOO_SMALL (the scratch), NO_DEVICE. */
+int fsehip_mcheck_build(const fsehip_pack_member* members, const void* const* d_bases, uint32_t n_members,
+                        uint8_t* d_record, uint8_t* d_scratch, uint64_t scratch_cap, fsehip_stream_t stream);
+
+/* Verify spans against the record at d_record, whose header `info` the caller
+ * has read: the members sel[0 .. n_sel) (each once), or all info->n_members
+ * for sel NULL.  which = 0: the member's n_elems * w bytes at d_ptrs[m] (a
+ * HOST array indexed by member; NULL: at members[m].d_ptr) against
+ * content_crc.  which = 1: a diff member's base at d_ptrs[m] against base_crc;
+ * without FSEHIP_MCHECK_BASES in info->flags nothing is read and every status
+ * is FSE_OK.  d_status[s] = FSE_OK or FSE_ERR_CHECKSUM per span, d_result[0] =
+ * FSE_OK, FSE_ERR_CHECKSUM when one failed, or FSE_ERR_BAD_FRAME (every status
+ * too) when the header on the device differs from `info`; d_result[1] = the
+ * spans that failed.  Asynchronous, three launches.  Checks as
+ * fsehip_mcheck_build, and BAD_ARG for members that do not sum to
+ * info->content_bytes or a selection out of range or named twice. */
+int fsehip_mcheck_verify(const fsehip_mcheck_info* info, const uint8_t* d_record, const fsehip_pack_member* members,
+                         const uint32_t* sel, uint32_t n_sel, uint32_t which, const void* const* d_ptrs,
+                         uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_status, int32_t* d_result,
+                         fsehip_stream_t stream);
+
+/* The sealed pack of the members at d_out: fsehip_pack_compress, or with
+ * d_bases fsehip_vpack_compress, straight to d_out + 32 + 8 n, then the
+ * record in front of it; with d_bases and check_bases the base CRCs are
+ * recorded.  *d_out_len includes the record.  d_scratch:
+ * fsehip_spack_scratch_bytes; out_cap: fsehip_spack_bound.  Statuses as the
+ * pack call's. */
+int fsehip_spack_compress(const fsehip_frame_params* p, const fsehip_pack_member* members, uint32_t n_members,
+                          const void* const* d_bases, uint32_t check_bases, uint8_t* d_scratch, uint64_t scratch_cap,
+                          uint8_t* d_out, uint64_t out_cap, uint64_t* d_out_len, int32_t* d_result,
+                          fsehip_stream_t stream);
+
+/* Decode the sealed pack at d_in (the record first; in_len the whole buffer).
+ * `rec`, `versioned` are fsehip_spack_read_header's, `info`, the members'
+ * fields and `inner` those of the pack reader at buf + inner_off; the other
+ * arguments are the pack call's.  d_member_check / d_base_check: one int32
+ * per member (per selected member), either may be NULL.  d_check_result[4]:
+ *   [0] FSE_OK, FSE_ERR_CHECKSUM when any verified member or base failed, or
+ *       FSE_ERR_BAD_FRAME when the record's header on the device differs from
+ *       the caller's (then every check status too)
+ *   [1] members whose content failed   [2] members whose base failed   [3] 0
+ * Order on the stream: the bases verified; the frame decoded into scratch; the
+ * pack head checked; the gate; the merge; the destinations verified.  The
+ * merge stores nothing when d_result[0] is BAD_FRAME, when a base failed or
+ * when the record's header differs.  Content verification always runs: its
+ * statuses say truthfully whether destination m holds the recorded content --
+ * after a closed gate, CHECKSUM wherever the new content differs from what
+ * lies there.  A buffer sealed without base CRCs decodes with every base
+ * status FSE_OK; a wrong base then shows as the member's CHECKSUM after the
+ * merge.  Asynchronous, no host synchronisation, a constant number of launches
+ * beyond the pack call's.  Before any device use: the pack call's statuses,
+ * and BAD_ARG for a record that does not agree with `info` or `versioned`. */
+int fsehip_spack_decompress(const fsehip_mcheck_info* rec, const fsehip_pack_info* info, uint32_t versioned,
+                            const fsehip_pack_member* members, const void* const* d_bases,
+                            const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in, uint64_t in_len,
+                            uint8_t* d_scratch, uint64_t scratch_cap, int32_t* d_block_status, int32_t* d_result,
+                            int32_t* d_member_check, int32_t* d_base_check, int32_t* d_check_result,
+                            fsehip_stream_t stream);
+int fsehip_spack_decompress_members(const fsehip_mcheck_info* rec, const fsehip_pack_info* info, uint32_t versioned,
+                                    const fsehip_pack_member* members, const void* const* d_bases,
+                                    const fsehip_frame_info* inner, uint32_t chunk_blocks, const uint8_t* d_in,
+                                    uint64_t in_len, const uint32_t* sel, uint32_t n_sel, uint8_t* d_scratch,
+                                    uint64_t scratch_cap, int32_t* d_member_status, int32_t* d_result,
+                                    int32_t* d_member_check, int32_t* d_base_check, int32_t* d_check_result,
+                                    fsehip_stream_t stream);
 
 /* ------------------------------------------------------------------------
  * (2c) Shared-table coding: many small messages against one caller's table
