@@ -15,7 +15,8 @@
 //                words at each lane boundary are OR-merged through LDS
 //      The encoder also records decode checkpoints (the sidecar index).
 // Also the utility kernels: histogram per block, pack/unpack/copy of
-// compressed blocks, the synthetic generator.  Decode: fse_decode.hip.
+// compressed blocks, the synthetic generator.  Decode: fse_decode.hip and
+// the fse_decode_*.hip files it names.
 
 #include "fse_device.hpp"
 #include "fse_kernels.h"

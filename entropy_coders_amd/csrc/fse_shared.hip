@@ -273,7 +273,7 @@ __global__ __launch_bounds__(SH_THREADS) void shared_encode_kernel(SharedParams 
 // bits, the next to be read on top; after every read it is refilled, so
 // nb >= 32 or no dword is left and "nb >= k" is the reader's "k bits remain"
 // (stack_reader.rs:176-215).  Output: 16-byte groups, the last one bytewise.
-// The end rules are the serial decoders' (fse_decode.hip, known / lim), but
+// The end rules are the serial decoders' (fse_decode_serial.hip, known / lim), but
 // that with a known length at two states the payload must end there too: the
 // block decoders stop at the raw length whatever follows.
 // ------------------------------------------------------------------------

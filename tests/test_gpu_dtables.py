@@ -202,14 +202,17 @@ def test_dtables_damaged_headers(torch_cuda, n_blocks):
     # (damaged headers often still parse: the oracle then gives the same other table)
 
 
-@pytest.mark.parametrize("log2", [0, 5, 6, 8, 10, 11])
+@pytest.mark.parametrize("log2", [0, 5, 6, 8, 10, 11, 12])
 def test_dtables_parallel_build_match_oracle(torch_cuda, log2):
-    """Batches of >= 256 blocks at L <= 11 build their tables from the
-    lane-parallel header parse (hdr_parse_kernel -> dtable_blocks_kernel):
+    """Batches of >= 256 blocks at L <= 12 build their tables from the
+    lane-parallel header parse (hdr_parse_kernel -> dtable_blocks_kernel; a
+    codec at table log 12 runs both at LMAX = 12, every other case at 11):
     every block's table against the oracle's DecodeTable entry for entry,
     over skewed / near-uniform (table_len > 64) / sparse / geometric blocks,
-    so -1 symbols, long zero runs and wide alphabets all occur.  (The same
-    test passed on the 4-wave dtable_par_kernel of the diagnostics build.)"""
+    so -1 symbols, long zero runs and wide alphabets all occur; then the
+    round trip on the tables built inside the call, and the first blocks'
+    bytes against the oracle's.  (The same test passed on the 4-wave
+    dtable_par_kernel of the diagnostics build.)"""
     torch = torch_cuda
     from entropy_coders_amd import BlockCodec
 
@@ -251,3 +254,10 @@ def test_dtables_parallel_build_match_oracle(torch_cuda, log2):
         checked += 1
         wide += int(sym.max()) >= 64
     assert checked >= nb_ * 3 // 4 and wide > 0, (checked, wide)
+    out, dst = codec.decompress(cb)
+    torch.cuda.synchronize()
+    ok = st == 0
+    assert (dst.cpu().numpy()[ok] == 0).all()
+    assert np.array_equal(out.cpu().numpy().reshape(nb_, bs)[ok], host.reshape(nb_, bs)[ok])
+    for b in np.flatnonzero(ok)[:8]:
+        assert codec.block_bytes(cb, int(b)) == O.compress2(blocks[b], log2 or None)[0], b

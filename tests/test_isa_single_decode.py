@@ -1,7 +1,7 @@
 """ISA check of the single-stream decoder's hand-scheduled scalar loads
 (CPU test on the built libfsehip.so; no GPU needed).
 
-single_decode_kernel (fse_decode.hip, fent_issue* / fent_wait* / fstep)
+single_decode_kernel (fse_decode_single.hip, fent_issue* / fent_wait* / fstep)
 issues `s_load_dwordx2` in one asm statement and waits for it with
 `s_waitcnt lgkmcnt(0)` in a later one.  The compiler does not track those
 loads, so the output is right only if no instruction touches a load's

@@ -2,7 +2,7 @@
 line tables (diagnostics, no GPU needed):
 
     hipcc -O3 -std=c++17 --offload-arch=gfx950 --cuda-device-only -gline-tables-only -S \
-        entropy_coders_amd/csrc/fse_decode.hip -o dec.s
+        entropy_coders_amd/csrc/fse_decode_seg.hip -o dec.s
     python tools/isa_valu_by_line.py dec.s decode_pre_kernelILi11ELj45056ELi2ELi1ELj512 [SOURCE_DIR]
 
 Every `v_*` instruction between the kernel's label and its end is charged to
